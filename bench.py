@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: keypoint-triangulations/s of the fused HIP triangulation path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg4|cfg5|cfg2_clean]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg4|cfg5|cfg2_clean] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (p2s_triangulate_device: stage + undistort/mask + weighted
 DLT + camera-subset search) over one synthetic batch that is already resident in HBM.  With
@@ -14,6 +14,7 @@ leg times the CPU oracle (oracle/, a loop-faithful port of the reference) on a b
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -72,6 +73,37 @@ def native_library_record():
         sha = None
     return {'file': os.path.relpath(path, ROOT), 'sha1_16': sha, 'compiled_by_this_run': rec.get('recompiled', []) if rec else None,
             'abi_version': int(_lib.load().p2s_version())}
+
+
+DUMP_BUDGET = 64_000_000  # --dump-outputs: bytes written at most (array data; the .npy headers fit in the margin below)
+DUMP_SEED = 20240          # --dump-outputs: seed of the sample taken from an output too large for the budget
+
+
+def dump_sample(n, bytes_per_item):
+    """Sorted indices of a fixed, seeded sample of n output items of bytes_per_item each (+ 8 B for the index itself),
+    as many as fit in DUMP_BUDGET with room to spare; all n items when they fit."""
+    m = min(n, (DUMP_BUDGET - 4_000_000) // (bytes_per_item + 8))
+    if m == n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False)).astype(np.int64)
+
+
+def where_valid(valid, a):
+    """a with the entries of the items that are not valid (NaN / inf there: rejected, nothing found) set to 0; which ones
+    those are travels in its own array, so that every value dumped is finite and compares with =="""
+    return np.where(valid.reshape(valid.shape + (1,) * (a.ndim - valid.ndim)), a, 0).astype(a.dtype)
+
+
+def write_dump(out_dir, arrays):
+    """arrays: name -> finite float32 / float64 host array; written as out_dir/<name>.npy (stderr notes where)."""
+    total = sum(a.nbytes for a in arrays.values())
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {k: a.dtype for k, a in arrays.items()}
+    assert all(np.isfinite(a).all() for a in arrays.values()), [k for k, a in arrays.items() if not np.isfinite(a).all()]
+    assert total <= DUMP_BUDGET, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a))
+    print(f'outputs of the last timed step: {len(arrays)} arrays, {total / 1e6:.1f} MB -> {out_dir}', file=sys.stderr, flush=True)
 
 
 def make_workload(cfg, rank):
@@ -152,12 +184,21 @@ def bench_association(args, cfg, rank, world, local_rank):
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        # the affinity matrices of a sample of frames; only the top-left N_f x N_f block of a frame is defined (0 elsewhere)
+        idx = dump_sample(F, n_max * n_max * 8 + 8)
+        aff = d_aff[torch.from_numpy(idx).to(dev)].cpu().numpy()
+        r, nf = np.arange(n_max), per_frame[idx]
+        valid = (r[None, :, None] < nf[:, None, None]) & (r[None, None, :] < nf[:, None, None])
+        dump = {'frame_index': idx.astype(np.float64), 'n_detections': nf.astype(np.float64), 'affinity': where_valid(valid, aff)}
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     if rank != 0:
         return
+    if args.dump_outputs:
+        write_dump(args.dump_outputs, dump)
     st = eng.assoc_stats()
     tflops = st['fp64_flops'] / dt / 1e12             # this rank's kernel; every rank runs the same workload shape
     out = {'metric': 'association-frames/sec', 'value': F * world * args.steps / dt, 'unit': 'frames/s',
@@ -289,6 +330,13 @@ def bench_single(args, cfg, rank, world, local_rank):
         dt = float(t.item())
     if rank != 0:
         return
+    if args.dump_outputs:
+        idx = dump_sample(F, C * 4 + 4 + 8 + 24)
+        h_err, h_Q = d_err.cpu().numpy()[idx], d_Q.cpu().numpy()[idx]
+        solved = np.isfinite(h_err)                        # inf: no combination could be triangulated
+        write_dump(args.dump_outputs, {'frame_index': idx.astype(np.float64), 'found': solved.astype(np.float32),
+                                       'combination': d_comb.cpu().numpy()[idx].astype(np.float32),
+                                       'error': where_valid(solved, h_err), 'Q': where_valid(solved, h_Q)})
     found = int(torch.isfinite(d_err).sum().item())
     out = {'metric': 'association-frames/sec', 'value': F * world * args.steps / dt, 'unit': 'frames/s',
            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3,
@@ -478,10 +526,17 @@ def main():
                          'before it runs at its sustained clocks (a 20-step run read 13 %% slower per kernel without; 0 = off)')
     ap.add_argument('--cpu-frames', type=int, default=0, help='frames for the cpu_baseline sample (0 = auto)')
     ap.add_argument('--e2e-frames', type=int, default=10_000, help='cfg3: frames of the association stage timed with its host half')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (rank 0: its shard) as DIR/<name>.npy, '
+                         'float32 / float64, at most 64 MB in all (a fixed, seeded sample of a larger output)')
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps is not None and args.steps < 1:
+        raise SystemExit('--steps must be >= 1')
+    if args.warmup is not None and args.warmup < 0:
+        raise SystemExit('--warmup must be >= 0')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # started as a plain `python bench.py --gpus N`: this process becomes the launcher (it has not touched the GPU
         # and never will) and the N ranks are fresh child processes; rank 0's JSON line goes to our stdout
@@ -600,6 +655,7 @@ def main():
     base = d_out.data_ptr()
     pending = [None, None]
     counter = [0]
+    period = n_buf * len(d_outs) // math.gcd(n_buf, len(d_outs))      # steps of one turn of the input / output rotation
 
     def step():
         i = counter[0] % len(d_outs)
@@ -647,6 +703,12 @@ def main():
                 flag = torch.tensor([1 if more else 0], dtype=torch.int32, device=dev)
                 dist.all_reduce(flag, op=dist.ReduceOp.MAX)
                 more = bool(int(flag.item()))
+        # the pre-roll ends on a whole turn of the buffer rotation: the warmup starts on input buffer 0 however long
+        # the pre-roll ran, so that step i after it reads the same input in every run (--dump-outputs)
+        while counter[0] % period:
+            step()
+        drain()
+        torch.cuda.synchronize()
     for _ in range(args.warmup):
         step()
     drain()
@@ -663,6 +725,16 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step wrote, taken on the launch stream before the roofline leg reuses the buffer; to the
+        # host after that leg.  A sample of the units where the whole result would exceed the budget.
+        last = d_outs[(counter[0] - 1) % len(d_outs)]
+        idx = dump_sample(n_units, 24 + 4 + 4 + 4 + 8)
+        d_idx = torch.from_numpy(idx).to(dev)
+        dump_dev = {'Q': last[:n_units * 24].view(torch.float64).view(n_units, 3)[d_idx],
+                    'err': last[off_e:off_e + n_units * 4].view(torch.float32)[d_idx],
+                    'n_excluded': last[off_n:off_n + n_units][d_idx],
+                    'camera_mask': last[off_m:off_m + n_units * 4].view(torch.int32)[d_idx]}
     if multi:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -750,6 +822,13 @@ def main():
                                  'value_kernels_only': n_units * world / (k_ms * 1e-3)}
         out.update(cpu if cpu else {'cpu_baseline': None})
         print(json.dumps(out), flush=True)
+        if args.dump_outputs:
+            host = {k: v.cpu().numpy() for k, v in dump_dev.items()}
+            accepted = np.isfinite(host['err'])           # a rejected unit has NaN error and NaN point (include/p2s.h)
+            write_dump(args.dump_outputs, {'unit_index': idx.astype(np.float64), 'accepted': accepted.astype(np.float32),
+                                           'Q': where_valid(accepted, host['Q']), 'err': where_valid(accepted, host['err']),
+                                           'n_excluded': host['n_excluded'].astype(np.float32),
+                                           'camera_mask': host['camera_mask'].view(np.uint32).astype(np.float64)})
     if multi:
         dist.destroy_process_group()
 
