@@ -197,6 +197,24 @@ int p2s_butterworth_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const d
 #define P2S_FILTER_KALMAN 5
 int p2s_filter_columns_host(p2s_ctx *ctx, int32_t kind, int64_t n_frames, int32_t n_cols, const double *data,
                             const double *params, int32_t n_params, double *out);
+/* gcv_spline_filter_1d (filtering.py:163-313) on every column of a row-major [n_frames][n_cols] float64 matrix: every run
+ * of >= 5 valid samples (not NaN, not 0) is replaced by the natural cubic smoothing spline through it, evaluated at its
+ * samples (scipy.interpolate.make_smoothing_spline(arange(n), run, lam=...)); other samples are copied.
+ *   auto_mode != 0  cut_off_frequency 'auto': the run is normalised, 1 + (run - median) / (1.4826 MAD) (MAD 0 -> 1),
+ *                   lambda minimises the GCV criterion on (0, n) (minimize_scalar 'bounded', xatol 1e-5, 500
+ *                   evaluations at most), the fit uses lambda * smoothing_factor and is denormalised; `lam` is ignored
+ *   auto_mode == 0  the fit uses lam * smoothing_factor on the raw run (the caller passes
+ *                   lam = (frame_rate / (2 pi cutoff))^4)
+ * lam_out [n_frames][n_cols] (may be NULL): the lambda of the final fit at the first sample of every filtered run, NaN
+ * elsewhere.  A run of 2 to 4 samples is refused as the reference refuses it (P2S_ERR_GCV_SHORT_RUN, checked before any
+ * launch); the first run (column by column) whose search or solve fails decides the status, and p2s_last_error() then
+ * holds the reference's message.  On any error `out` holds the input.  HOST pointers; blocks. */
+#define P2S_ERR_GCV_SHORT_RUN (-6)     /* "``x`` and ``y`` length must be at least 5"                              */
+#define P2S_ERR_GCV_ILL_POSED (-7)     /* the banded Cholesky factorisation failed: "Seems like the problem is ill-posed" */
+#define P2S_ERR_GCV_NO_MINIMUM (-8)    /* the search hit 500 evaluations or a NaN: "Unable to find minimum of ..."  */
+#define P2S_ERR_GCV_SINGULAR (-9)      /* a zero pivot in the banded LU solve: "singular matrix"                    */
+int p2s_gcv_spline_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const double *data, int32_t auto_mode,
+                        double lam, double smoothing_factor, double *out, double *lam_out);
 /* trc_evaluate's per-frame quantities and sums (Utilities/trc_evaluate.py:114-238) for xyz [n_frames][n_markers][3]:
  *   bones      [n_bones][2] int32  (parent, child) marker indices
  *   bone_len   [n_bones][n_frames]      |child - parent|, 0 -> NaN             (compute_bone_lengths :135-139)

@@ -144,7 +144,9 @@ def triangulation(config=None):
 
 
 def filtering(config=None):
-    """Butterworth filtering of the .trc files (the other filter types are refused by filtering.filter_all)."""
+    """Filtering of the .trc files (filtering.filter_all): every filter type of the reference's filter_mapping --
+    butterworth, butterworth_on_speed, gaussian, median, one_euro, kalman and gcv_spline -- except loess, which is
+    refused with NotImplementedError."""
     _run_stage('filtering', config)
 
 

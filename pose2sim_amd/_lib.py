@@ -15,6 +15,8 @@ P2S_MAX_PERSONS_TOTAL = 48
 P2S_MAX_PERSONS_PER_CAM = 16
 P2S_MAX_COMBINATIONS = 1 << 20
 P2S_JSON_UNREADABLE, P2S_JSON_NO_PEOPLE_LIST = -1, -2
+P2S_ERR_INVALID_ARG = -1
+P2S_ERR_GCV_SHORT_RUN, P2S_ERR_GCV_ILL_POSED, P2S_ERR_GCV_NO_MINIMUM, P2S_ERR_GCV_SINGULAR = -6, -7, -8, -9
 P2S_JSON_PERSON_NO_LIST, P2S_JSON_PERSON_NOT_NUMERIC = -1, -2
 
 
@@ -71,6 +73,7 @@ SIGNATURES = {
     'p2s_get_assoc_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     'p2s_butterworth_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'p2s_filter_columns_host': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    'p2s_gcv_spline_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     'p2s_trc_metrics_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'p2s_timing_begin': (C.c_int, [C.c_void_p]),
     'p2s_timing_end': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
@@ -93,6 +96,9 @@ SIGNATURES = {
                                    C.POINTER(C.c_int32)]),
 }
 
+# entry points a library built before them lacks (P2S_LIB may name one): left unbound, and the feature is refused
+OPTIONAL = {'p2s_gcv_spline_host'}
+
 _lib = None
 
 
@@ -110,6 +116,8 @@ def load():
                        '(hipcc --offload-arch=gfx950). There is no CPU fallback.')
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
+        if name in OPTIONAL and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -891,6 +891,126 @@ int p2s_filter_columns_host(p2s_ctx *ctx, int32_t kind, int64_t n_frames, int32_
     return P2S_OK;
 }
 
+namespace {
+
+// np.median of v (destroyed): the middle order statistic, or the mean of the two middle ones
+double median_of(std::vector<double> &v) {
+    const size_t n = v.size(), h = n / 2;
+    std::nth_element(v.begin(), v.begin() + h, v.end());
+    const double hi = v[h];
+    if (n % 2) return hi;
+    const double lo = *std::max_element(v.begin(), v.begin() + h);
+    return (lo + hi) / 2.0;
+}
+
+}  // namespace
+
+int p2s_gcv_spline_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const double *data, int32_t auto_mode,
+                        double lam, double smoothing_factor, double *out, double *lam_out) {
+    if (!ctx) return fail(P2S_ERR_INVALID_ARG, "null context");
+    if (n_frames < 0 || n_frames > INT32_MAX || n_cols < 0)
+        return fail(P2S_ERR_INVALID_ARG, "bad shape: n_frames=%lld n_cols=%d", (long long)n_frames, n_cols);
+    if (n_frames == 0 || n_cols == 0) return P2S_OK;
+    if (!data || !out) return fail(P2S_ERR_INVALID_ARG, "null pointer");
+    const int64_t S = n_cols;
+    const size_t total = (size_t)n_frames * n_cols;
+    std::memcpy(out, data, total * sizeof(double));
+    if (lam_out)
+        for (size_t i = 0; i < total; ++i) lam_out[i] = NAN;
+
+    // the runs of valid samples (neither NaN nor 0, filtering.py:265-270), column by column
+    std::vector<P2sGcvRun> runs;
+    std::vector<double> tmp;
+    for (int32_t c = 0; c < n_cols; ++c) {
+        int64_t f = 0;
+        while (f < n_frames) {
+            auto valid = [&](int64_t i) { const double v = data[i * S + c]; return v == v && v != 0.0; };
+            if (!valid(f)) { ++f; continue; }
+            int64_t r = f + 1;
+            while (r < n_frames && valid(r)) ++r;
+            const int64_t len = r - f;
+            if (len >= 2 && len <= 4)                      // make_smoothing_spline / the GCV helper refuse n <= 4
+                return fail(P2S_ERR_GCV_SHORT_RUN, "``x`` and ``y`` length must be at least 5");
+            if (len >= 5) {
+                P2sGcvRun run{};
+                run.col = c; run.start = (int32_t)f; run.len = (int32_t)len;
+                run.med = 0.0; run.scale = 1.0;
+                for (int64_t i = f; i < r; ++i)
+                    if (std::isinf(data[i * S + c])) return fail(P2S_ERR_INVALID_ARG, "array must not contain infs or NaNs");
+                if (auto_mode) {                           // filtering.py:277-281
+                    tmp.assign(len, 0.0);
+                    for (int64_t i = 0; i < len; ++i) tmp[i] = data[(f + i) * S + c];
+                    const double med = median_of(tmp);
+                    for (int64_t i = 0; i < len; ++i) tmp[i] = std::fabs(data[(f + i) * S + c] - med);
+                    double mad = median_of(tmp);
+                    mad = mad > 0 ? mad : 1.0;
+                    run.med = med;
+                    run.scale = 1.4826 * mad;
+                }
+                runs.push_back(run);
+            }
+            f = r;
+        }
+    }
+    if (runs.empty()) return P2S_OK;
+    if (!((auto_mode ? smoothing_factor : lam * smoothing_factor) >= 0.0))
+        return fail(P2S_ERR_INVALID_ARG, "Regularization parameter should be non-negative");
+
+    // longest first, so that the long runs start first and a wave's lanes have similar lengths; the factor storage of
+    // a wave covers its longest run
+    std::vector<int32_t> order(runs.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = (int32_t)i;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return runs[x].len > runs[y].len; });
+    std::vector<P2sGcvRun> sorted(runs.size());
+    size_t work_doubles = 0;
+    for (size_t i = 0; i < order.size(); ++i) {
+        sorted[i] = runs[order[i]];
+        if (i % 64 == 0) {
+            sorted[i].work_off = (int64_t)work_doubles;
+            work_doubles += (size_t)sorted[i].len * P2S_GCV_SLOTS * 64;
+        } else {
+            sorted[i].work_off = sorted[i - i % 64].work_off;
+        }
+    }
+
+    P2sGcvArgs g{};
+    g.n_frames = n_frames; g.n_cols = n_cols; g.n_runs = (int32_t)sorted.size();
+    g.auto_mode = auto_mode ? 1 : 0;
+    g.fixed_lam = lam * smoothing_factor;                  // filtering.py:301-304
+    g.smoothing_factor = smoothing_factor;
+    const size_t bytes = total * sizeof(double), run_bytes = sorted.size() * sizeof(P2sGcvRun);
+    int rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = ctx->q.ensure(bytes)) != P2S_OK) return rc;
+    if ((rc = ctx->in.ensure(run_bytes)) != P2S_OK) return rc;
+    if ((rc = ctx->aux0.ensure(work_doubles * sizeof(double))) != P2S_OK) return rc;
+    g.data = (double *)ctx->q.p; g.runs = (P2sGcvRun *)ctx->in.p; g.work = (double *)ctx->aux0.p;
+    HIP_TRY(hipMemcpyAsync(ctx->q.p, data, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->in.p, sorted.data(), run_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(p2s_launch_gcv_spline(g, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, ctx->q.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(sorted.data(), ctx->in.p, run_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+
+    // the reference stops at the first run (column by column) whose search or solve fails
+    const P2sGcvRun *bad = nullptr;
+    for (const P2sGcvRun &r : sorted)
+        if (r.status != P2S_GCV_OK && (!bad || r.col < bad->col || (r.col == bad->col && r.start < bad->start))) bad = &r;
+    if (bad) {
+        std::memcpy(out, data, bytes);
+        switch (bad->status) {
+        case P2S_GCV_ILL_POSED: return fail(P2S_ERR_GCV_ILL_POSED, "Seems like the problem is ill-posed");
+        case P2S_GCV_SINGULAR: return fail(P2S_ERR_GCV_SINGULAR, "singular matrix");
+        case P2S_GCV_MAX_EVALS:
+            return fail(P2S_ERR_GCV_NO_MINIMUM, "Unable to find minimum of the GCV function: Maximum number of function calls reached.");
+        default: return fail(P2S_ERR_GCV_NO_MINIMUM, "Unable to find minimum of the GCV function: NaN result encountered.");
+        }
+    }
+    if (lam_out)
+        for (const P2sGcvRun &r : sorted) lam_out[(int64_t)r.start * S + r.col] = r.lam;
+    return P2S_OK;
+}
+
 int p2s_trc_metrics_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_markers, const double *xyz, int32_t n_bones,
                          const int32_t *bones, double *bone_len, double *bone_stats, double *accel, int64_t *missing) {
     if (!ctx) return fail(P2S_ERR_INVALID_ARG, "null context");

@@ -417,6 +417,344 @@ __global__ void __launch_bounds__(256) p2s_trc_metrics_kernel(const P2sMetricsAr
     if (tid == 0) a.missing[m] = (int64_t)s_cnt[0];
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// gcv_spline_filter_1d (filtering.py:163-313): natural cubic smoothing spline of every run of >= 5 valid samples, with
+// lambda either fixed or chosen by generalised cross-validation (scipy.interpolate.make_smoothing_spline).
+//
+// The samples sit at x = 0, 1, ..., n - 1.  The spline is written in the cubic B-spline basis on the knots x with
+// four-fold end knots; the natural end conditions s''(x_0) = s''(x_{n-1}) = 0 fix the two outermost B-spline
+// coefficients at either end from their neighbours, which leaves n free coefficients c (Wahba 1990, ch. 2; the change
+// of basis is make_smoothing_spline's documented one).  In that basis
+//   X  [n][n]  the spline's values at the samples (s = X c): the uniform cubic B-spline's 1/6, 2/3, 1/6 on three
+//              diagonals, and at either end the basis functions that absorbed the boundary coefficients
+//   E  [n][n]  the penalty: Wahba's divided-difference form, 6 (x_{j+2} - x_{j-2}) [x_{j-2}..x_{j+2}] on column j,
+//              i.e. the fourth difference 1 -4 6 -4 1, with the 3- and 4-point divided differences in the two
+//              outermost columns at either end (unit weights, so W^-1 E = E)
+// and the coefficients of lambda solve the 5-band, non-symmetric system (X + lambda E) c = y.  GCV(lambda) =
+// (|lambda E c|^2 / n) / (1 - tr(A) / n)^2 (Wahba 1990, 4.3; Craven & Wahba 1979); the trace of the influence matrix A
+// is sum_ij B_ij (X^T X)_ij with B = (X^T X + lambda X^T E)^-1 needed on its three central bands only, which Hutchinson
+// & de Hoog (1985) get from the banded Cholesky factor U^T D^-1 U by a backward recurrence.  lambda minimises GCV on
+// (0, n) by scipy.optimize.minimize_scalar(method='bounded') (Brent's method with golden-section start, xatol 1e-5,
+// 500 evaluations at most).
+//
+// Operation order follows what scipy calls: the 5-band solve is LAPACK gbsv (unblocked band LU with partial pivoting on
+// the first largest |pivot|, multipliers by the reciprocal pivot, then the column-oriented band back-substitution),
+// the Cholesky factor is pbtrf('U') (reciprocal scaling, rank-1 trailing updates), the band products of X^T X and
+// X^T E are summed row by row, and no operation is contracted into an FMA.  Sums over the samples (the trace, |E c|^2)
+// run backwards here, so the GCV values agree with scipy's to rounding, not bit for bit.
+//
+// One lane per run: the search is sequential in lambda and an evaluation is sequential in the samples.  An evaluation
+// is two sweeps over the run: forwards, the LU of X + lambda E with the elimination of y and, independent of it, the
+// Cholesky factorisation of X^T X + lambda X^T E (both in registers over a sliding window, the bands computed on the
+// fly); backwards, the back-substitution with |lambda E c|^2 and, again independent, the inverse-band recurrence with
+// the trace.  The factors the backward sweep needs (U row of the LU, eliminated y, normalised Cholesky row and D) are
+// the 10 slots per sample the forward sweep leaves in `work`; slot 10 holds the run's (normalised) samples.
+namespace gcv {
+
+constexpr double kSixth = 0x1.5555555555555p-3, kTwoThirds = 0x1.5555555555555p-1;   // 1/6, 2/3 rounded
+constexpr double kEdge = kSixth + kTwoThirds;                                           // B_1 + B_2 at x_1
+constexpr double kSqrtEps = 0x1.fda324be34921p-27;          // sqrt(2.2e-16), minimize_scalar's constant
+constexpr double kGolden = 0x1.8722191a02d60p-2;            // 0.5 (3 - sqrt(5))
+constexpr double kXatol = 1e-5;
+constexpr int kMaxFun = 500;
+enum { kU0 = 0, kYe = 5, kC1 = 6, kD = 9, kY = 10 };          // work slots
+
+// X[r][c]: column c's basis function at sample r (nonzero for |r - c| <= 1)
+__host__ __device__ __forceinline__ double xb(int64_t r, int64_t c, int64_t n) {
+    const int64_t d = r - c;
+    if (r < 0 || r >= n || c < 0 || c >= n || d < -1 || d > 1) return 0.0;
+    if (c >= 2 && c <= n - 3) return d == 0 ? kTwoThirds : kSixth;
+    if (c == 0) return d == 0 ? 3.0 : 0.5;
+    if (c == n - 1) return d == 0 ? 3.0 : 0.5;
+    if (c == 1) return d == -1 ? 1.0 : (d == 0 ? kEdge : kSixth);
+    return d == 1 ? 1.0 : (d == 0 ? kEdge : kSixth);                 // c == n - 2
+}
+
+// E[r][c]: the penalty (nonzero for |r - c| <= 2)
+__host__ __device__ __forceinline__ double eb(int64_t r, int64_t c, int64_t n) {
+    const int64_t d = r - c;
+    if (r < 0 || r >= n || c < 0 || c >= n || d < -2 || d > 2) return 0.0;
+    if (c >= 2 && c <= n - 3) return d == 0 ? 6.0 : ((d == 1 || d == -1) ? -4.0 : 1.0);
+    if (c == 0) return d == 0 ? 3.0 : (d == 1 ? -6.0 : (d == 2 ? 3.0 : 0.0));
+    if (c == n - 1) return d == 0 ? 3.0 : (d == -1 ? -6.0 : (d == -2 ? 3.0 : 0.0));
+    if (c == 1) return d == -1 ? -1.0 : (d == 0 ? 3.0 : (d == 1 ? -3.0 : (d == 2 ? 1.0 : 0.0)));
+    return d == -2 ? 1.0 : (d == -1 ? -3.0 : (d == 0 ? 3.0 : (d == 1 ? -1.0 : 0.0)));   // c == n - 2
+}
+
+// (X^T X)[i][i + j] and (X^T E)[i][i + j], j = 0..3, summed over the rows in ascending order
+__host__ __device__ __forceinline__ double xtx(int64_t i, int j, int64_t n) {
+#pragma clang fp contract(off)
+    if (i + j >= n) return 0.0;
+    double s = 0.0;
+    for (int k = j; k < 5; ++k) s = s + xb(i + k - 2, i, n) * xb(i + k - 2, i + j, n);
+    return s;
+}
+__host__ __device__ __forceinline__ double xte(int64_t i, int j, int64_t n) {
+#pragma clang fp contract(off)
+    if (i + j >= n) return 0.0;
+    double s = 0.0;
+    for (int k = j; k < 5; ++k) s = s + xb(i + k - 2, i, n) * eb(i + k - 2, i + j, n);
+    return s;
+}
+
+struct Lane {
+    double *w;                   // slot k of sample i at w[i * ss + k * ks]
+    int64_t ss, ks, n;
+    double xx[4], xe[4];         // the interior values of the two band products
+    __host__ __device__ double &at(int64_t i, int k) const { return w[i * ss + k * ks]; }
+    __host__ __device__ double XX(int64_t i, int j) const { return (i >= 2 && i + j <= n - 3) ? xx[j] : xtx(i, j, n); }
+    __host__ __device__ double XE(int64_t i, int j) const { return (i >= 2 && i + j <= n - 3) ? xe[j] : xte(i, j, n); }
+};
+
+__host__ __device__ inline void lane_init(Lane &L) {
+    for (int j = 0; j < 4; ++j) { L.xx[j] = xtx(4, j, 12); L.xe[j] = xte(4, j, 12); }
+}
+
+// Forward sweep for one lambda: LU of X + lambda E with the elimination of y (slot kY) -> U rows and eliminated y; with
+// kChol also the Cholesky factor of X^T X + lambda X^T E -> U_ij / U_ii (j = i+1..i+3) and D_i = 1 / U_ii^2.
+template <bool kChol>
+__host__ __device__ int forward(const Lane &L, double lam) {
+#pragma clang fp contract(off)
+    const int64_t n = L.n;
+    auto M = [&](int64_t r, int64_t c) { return xb(r, c, n) + lam * eb(r, c, n); };
+    auto A = [&](int64_t i, int j) { return L.XX(i, j) + lam * L.XE(i, j); };
+    double R0[5], R1[5], R2[5];                       // rows j, j+1, j+2 over columns j..j+4
+    for (int k = 0; k < 5; ++k) { R0[k] = M(0, k); R1[k] = M(1, k); R2[k] = M(2, k); }
+    double y0 = L.at(0, kY), y1 = L.at(1, kY), y2 = L.at(2, kY);
+    // Cholesky window: the partly updated upper triangle of rows/columns j..j+3
+    double w00 = 0, w01 = 0, w02 = 0, w03 = 0, w11 = 0, w12 = 0, w13 = 0, w22 = 0, w23 = 0, w33 = 0;
+    if (kChol) {
+        w00 = A(0, 0); w01 = A(0, 1); w02 = A(0, 2); w03 = A(0, 3);
+        w11 = A(1, 0); w12 = A(1, 1); w13 = A(1, 2); w22 = A(2, 0); w23 = A(2, 1); w33 = A(3, 0);
+    }
+    for (int64_t j = 0; j < n; ++j) {
+        // LU, column j: pivot = first largest |.| among the rows j..j+km
+        const int64_t km = (n - 1 - j) < 2 ? (n - 1 - j) : 2;
+        int p = 0;
+        double amax = fabs(R0[0]);
+        if (km >= 1 && fabs(R1[0]) > amax) { p = 1; amax = fabs(R1[0]); }
+        if (km >= 2 && fabs(R2[0]) > amax) p = 2;
+        if (p == 1) {
+            for (int k = 0; k < 5; ++k) { const double t = R0[k]; R0[k] = R1[k]; R1[k] = t; }
+            const double t = y0; y0 = y1; y1 = t;
+        } else if (p == 2) {
+            for (int k = 0; k < 5; ++k) { const double t = R0[k]; R0[k] = R2[k]; R2[k] = t; }
+            const double t = y0; y0 = y2; y2 = t;
+        }
+        if (R0[0] == 0.0) return P2S_GCV_SINGULAR;
+        const double rinv = 1.0 / R0[0];
+        const double l1 = R1[0] * rinv, l2 = R2[0] * rinv;
+        for (int k = 1; k < 5; ++k) { R1[k] = R1[k] - l1 * R0[k]; R2[k] = R2[k] - l2 * R0[k]; }
+        y1 = y1 - l1 * y0;
+        y2 = y2 - l2 * y0;
+        for (int k = 0; k < 5; ++k) L.at(j, kU0 + k) = R0[k];
+        L.at(j, kYe) = y0;
+        for (int k = 0; k < 4; ++k) { R0[k] = R1[k + 1]; R1[k] = R2[k + 1]; }
+        R0[4] = 0.0; R1[4] = 0.0;
+        for (int k = 0; k < 5; ++k) R2[k] = M(j + 3, j + 1 + k);
+        y0 = y1; y1 = y2;
+        y2 = (j + 3 < n) ? L.at(j + 3, kY) : 0.0;
+
+        if (kChol) {
+            // Cholesky, row j (pbtf2 'U'): U_jj = sqrt(a_jj), U_j,j+k = a_j,j+k * (1 / U_jj), trailing rank-1 update
+            if (!(w00 > 0.0)) return P2S_GCV_ILL_POSED;
+            const double ajj = sqrt(w00);
+            const double ri = 1.0 / ajj;
+            const double u1 = w01 * ri, u2 = w02 * ri, u3 = w03 * ri;
+            w11 = w11 - u1 * u1; w12 = w12 - u1 * u2; w13 = w13 - u1 * u3;
+            w22 = w22 - u2 * u2; w23 = w23 - u2 * u3;
+            w33 = w33 - u3 * u3;
+            L.at(j, kC1) = u1 / ajj; L.at(j, kC1 + 1) = u2 / ajj; L.at(j, kC1 + 2) = u3 / ajj;
+            L.at(j, kD) = 1.0 / (ajj * ajj);
+            w00 = w11; w01 = w12; w02 = w13; w03 = A(j + 1, 3);
+            w11 = w22; w12 = w23; w13 = A(j + 2, 2);
+            w22 = w33; w23 = A(j + 3, 1);
+            w33 = A(j + 4, 0);
+        }
+    }
+    return P2S_GCV_OK;
+}
+
+// Backward sweep after forward<true>: c by back-substitution, |lambda E c|^2, the inverse's central bands and the
+// trace -> GCV(lambda).
+__host__ __device__ double backward_gcv(const Lane &L, double lam) {
+#pragma clang fp contract(off)
+    const int64_t n = L.n;
+    double c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0;          // c_i .. c_{i+4}
+    double sq = 0.0, tr = 0.0;
+    double p0 = 0, p1 = 0, p2 = 0, q0 = 0, q1 = 0, r0 = 0;   // B bands 0..2 of row i+1, 0..1 of row i+2, 0 of row i+3
+    auto resid = [&](int64_t m, double a0, double a1, double a2, double a3, double a4) {
+        // (E c)_m, columns m+2 down to m-2 (c_{m-2+k} = a_k); (lambda (E c)_m)^2
+        double s = 0.0;
+        s = s + eb(m, m + 2, n) * a4; s = s + eb(m, m + 1, n) * a3; s = s + eb(m, m, n) * a2;
+        s = s + eb(m, m - 1, n) * a1; s = s + eb(m, m - 2, n) * a0;
+        const double v = lam * s;
+        return v * v;
+    };
+    for (int64_t i = n - 1; i >= 0; --i) {
+        const double *u = &L.at(i, kU0);
+        const double ci = ((((L.at(i, kYe) - c3 * u[4 * L.ks]) - c2 * u[3 * L.ks]) - c1 * u[2 * L.ks]) - c0 * u[L.ks]) / u[0];
+        c4 = c3; c3 = c2; c2 = c1; c1 = c0; c0 = ci;
+        if (i + 2 <= n - 1) sq = sq + resid(i + 2, c0, c1, c2, c3, c4);
+
+        const double U1 = L.at(i, kC1), U2 = L.at(i, kC1 + 1), U3 = L.at(i, kC1 + 2), D = L.at(i, kD);
+        const double b3 = ((0.0 - U1 * p2) - U2 * q1) - U3 * r0;
+        const double b2 = ((0.0 - U1 * p1) - U2 * q0) - U3 * q1;
+        const double b1 = ((0.0 - U1 * p0) - U2 * p1) - U3 * p2;
+        const double b0 = (((0.0 - U1 * b1) - U2 * b2) - U3 * b3) + D;
+        if (i + 2 <= n - 1)                                   // column i+2 of tr = B * X^T X (off-diagonals twice)
+            tr = tr + (((b2 * L.XX(i, 2)) * 2.0 + (p1 * L.XX(i + 1, 1)) * 2.0) + q0 * L.XX(i + 2, 0));
+        r0 = q0; q0 = p0; q1 = p1;
+        p0 = b0; p1 = b1; p2 = b2;
+    }
+    // columns 1 and 0 of the residual and the trace
+    sq = sq + resid(1, 0.0, c0, c1, c2, c3);
+    sq = sq + resid(0, 0.0, 0.0, c0, c1, c2);
+    tr = tr + ((p1 * L.XX(0, 1)) * 2.0 + q0 * L.XX(1, 0));
+    tr = tr + p0 * L.XX(0, 0);
+    const double norm = sqrt(sq);
+    const double numer = norm * norm / (double)n;
+    const double t = 1.0 - tr / (double)n;
+    return numer / (t * t);
+}
+
+// Backward sweep of the final fit: c, then s = X c at the samples, written to out[i * stride] (denormalised in 'auto').
+__host__ __device__ void backward_fit(const Lane &L, double *out, int64_t stride, bool denorm, double scale, double med) {
+#pragma clang fp contract(off)
+    const int64_t n = L.n;
+    double c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    auto emit = [&](int64_t i, double s) { out[i * stride] = denorm ? (s - 1.0) * scale + med : s; };
+    for (int64_t i = n - 1; i >= 0; --i) {
+        const double *u = &L.at(i, kU0);
+        const double ci = ((((L.at(i, kYe) - c3 * u[4 * L.ks]) - c2 * u[3 * L.ks]) - c1 * u[2 * L.ks]) - c0 * u[L.ks]) / u[0];
+        c3 = c2; c2 = c1; c1 = c0; c0 = ci;
+        if (i + 1 <= n - 1) emit(i + 1, (xb(i + 1, i, n) * c0 + xb(i + 1, i + 1, n) * c1) + xb(i + 1, i + 2, n) * c2);
+    }
+    emit(0, xb(0, 0, n) * c0 + xb(0, 1, n) * c1);
+}
+
+__host__ __device__ inline double nan_max(double a, double b) { return (a != a || b != b) ? a + b : (a > b ? a : b); }
+__host__ __device__ inline double sign(double v) { return v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : (v == 0.0 ? 0.0 : v)); }
+
+// One run: the (normalised) samples are in slot kY.  Returns P2S_GCV_*; lam_out = the lambda of the final fit.
+__host__ __device__ int run(Lane &L, bool auto_mode, double fixed_lam, double sf, double *out, int64_t stride,
+                            double scale, double med, double *lam_out, int32_t *n_eval) {
+#pragma clang fp contract(off)
+    lane_init(L);
+    double lam = fixed_lam;
+    *n_eval = 0;
+    if (auto_mode) {
+        int status = P2S_GCV_OK;
+        auto f = [&](double x) -> double {
+            if (status != P2S_GCV_OK) return 0.0;
+            const int st = forward<true>(L, x);
+            if (st != P2S_GCV_OK) { status = st; return 0.0; }
+            return backward_gcv(L, x);
+        };
+        // scipy.optimize._optimize._minimize_scalar_bounded on (0, n)
+        double a = 0.0, b = (double)L.n;
+        double fulc = a + kGolden * (b - a);
+        double nfc = fulc, xf = fulc;
+        double rat = 0.0, e = 0.0;
+        double x = xf;
+        double fx = f(x);
+        int num = 1;
+        double fu = INFINITY;
+        double ffulc = fx, fnfc = fx;
+        double xm = 0.5 * (a + b);
+        double tol1 = kSqrtEps * fabs(xf) + kXatol / 3.0;
+        double tol2 = 2.0 * tol1;
+        int flag = 0;
+        while (status == P2S_GCV_OK && fabs(xf - xm) > (tol2 - 0.5 * (b - a))) {
+            bool golden = true;
+            if (fabs(e) > tol1) {
+                golden = false;
+                double r = (xf - nfc) * (fx - ffulc);
+                double q = (xf - fulc) * (fx - fnfc);
+                double p = (xf - fulc) * q - (xf - nfc) * r;
+                q = 2.0 * (q - r);
+                if (q > 0.0) p = -p;
+                q = fabs(q);
+                r = e;
+                e = rat;
+                if ((fabs(p) < fabs(0.5 * q * r)) && (p > q * (a - xf)) && (p < q * (b - xf))) {
+                    rat = (p + 0.0) / q;
+                    x = xf + rat;
+                    if (((x - a) < tol2) || ((b - x) < tol2)) {
+                        const double si = sign(xm - xf) + ((xm - xf) == 0.0 ? 1.0 : 0.0);
+                        rat = tol1 * si;
+                    }
+                } else {
+                    golden = true;
+                }
+            }
+            if (golden) {
+                e = (xf >= xm) ? a - xf : b - xf;
+                rat = kGolden * e;
+            }
+            const double si = sign(rat) + (rat == 0.0 ? 1.0 : 0.0);
+            x = xf + si * nan_max(fabs(rat), tol1);
+            fu = f(x);
+            num += 1;
+            if (fu <= fx) {
+                if (x >= xf) a = xf; else b = xf;
+                fulc = nfc; ffulc = fnfc;
+                nfc = xf; fnfc = fx;
+                xf = x; fx = fu;
+            } else {
+                if (x < xf) a = x; else b = x;
+                if ((fu <= fnfc) || (nfc == xf)) {
+                    fulc = nfc; ffulc = fnfc;
+                    nfc = x; fnfc = fu;
+                } else if ((fu <= ffulc) || (fulc == xf) || (fulc == nfc)) {
+                    fulc = x; ffulc = fu;
+                }
+            }
+            xm = 0.5 * (a + b);
+            tol1 = kSqrtEps * fabs(xf) + kXatol / 3.0;
+            tol2 = 2.0 * tol1;
+            if (num >= kMaxFun) { flag = 1; break; }
+        }
+        *n_eval = num;
+        if (status != P2S_GCV_OK) return status;
+        if (xf != xf || fx != fx || fu != fu) flag = 2;
+        if (flag == 1) return P2S_GCV_MAX_EVALS;
+        if (flag == 2) return P2S_GCV_NAN;
+        lam = xf * sf;
+    }
+    *lam_out = lam;
+    const int st = forward<false>(L, lam);
+    if (st != P2S_GCV_OK) return st;
+    backward_fit(L, out, stride, auto_mode, scale, med);
+    return P2S_GCV_OK;
+}
+
+}  // namespace gcv
+
+__global__ void __launch_bounds__(64) p2s_gcv_spline_kernel(const P2sGcvArgs a) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x * 64 + threadIdx.x;
+    if (r >= a.n_runs) return;
+    P2sGcvRun &run = a.runs[r];
+    const int64_t S = a.n_cols, n = run.len;
+    double *col = a.data + (int64_t)run.start * S + run.col;
+    gcv::Lane L;
+    L.w = a.work + run.work_off + threadIdx.x;
+    L.ks = 64;
+    L.ss = (int64_t)P2S_GCV_SLOTS * 64;
+    L.n = n;
+    for (int64_t i = 0; i < n; ++i) {                          // the run, normalised in 'auto' (filtering.py:281)
+        const double v = col[i * S];
+        L.at(i, gcv::kY) = a.auto_mode ? 1.0 + (v - run.med) / run.scale : v;
+    }
+    double lam = __builtin_nan("");
+    int32_t n_eval = 0;
+    const int st = gcv::run(L, a.auto_mode != 0, a.fixed_lam, a.smoothing_factor, col, S, run.scale, run.med, &lam, &n_eval);
+    run.lam = lam;
+    run.n_eval = n_eval;
+    run.status = st;
+}
+
 }  // namespace
 
 hipError_t p2s_launch_butter(const P2sFilterArgs &a, hipStream_t s) {
@@ -454,5 +792,12 @@ hipError_t p2s_launch_trc_metrics(const P2sMetricsArgs &a, hipStream_t s) {
     const unsigned grid = (unsigned)(a.n_bones + a.n_markers);
     if (grid == 0) return hipSuccess;
     hipLaunchKernelGGL(p2s_trc_metrics_kernel, dim3(grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t p2s_launch_gcv_spline(const P2sGcvArgs &a, hipStream_t s) {
+    if (a.n_runs == 0) return hipSuccess;
+    const unsigned grid = (unsigned)((a.n_runs + 63) / 64);
+    hipLaunchKernelGGL(p2s_gcv_spline_kernel, dim3(grid), dim3(64), 0, s, a);
     return hipGetLastError();
 }

@@ -186,6 +186,34 @@ struct P2sColFilterArgs {
 };
 hipError_t p2s_launch_col_filter(const P2sColFilterArgs &a, hipStream_t s);
 
+// gcv_spline_filter_1d: one lane per run of >= 5 valid samples.  The host sorts the runs longest first; run r is lane
+// r % 64 of wave r / 64, whose factor storage starts at work_off doubles into `work`: [sample][P2S_GCV_SLOTS][64 lanes]
+// over the wave's longest run.
+#define P2S_GCV_SLOTS 11
+#define P2S_GCV_OK 0
+#define P2S_GCV_ILL_POSED 1          // the banded Cholesky factorisation failed (scipy: 'Seems like the problem is ill-posed')
+#define P2S_GCV_MAX_EVALS 2          // minimize_scalar stopped at maxiter = 500 evaluations
+#define P2S_GCV_NAN 3                // minimize_scalar met a NaN
+#define P2S_GCV_SINGULAR 4           // a zero pivot in the banded LU solve (LAPACK gbsv info > 0)
+struct P2sGcvRun {
+    int64_t work_off;            // doubles into P2sGcvArgs::work of this run's wave
+    int32_t col, start, len;     // column, first frame, number of samples (>= 5)
+    int32_t n_eval;              // out: GCV evaluations of the search ('auto')
+    double med, scale;           // 'auto': the run's median and 1.4826 * MAD (MAD 0 -> 1)
+    double lam;                  // out: the lambda of the final fit
+    int32_t status, pad;         // out: P2S_GCV_*
+};
+struct P2sGcvArgs {
+    double *data;                // [n_frames][n_cols]: read, and the filtered runs written in place
+    P2sGcvRun *runs;             // [n_runs]
+    double *work;
+    int64_t n_frames;
+    int32_t n_cols, n_runs;
+    int32_t auto_mode;           // 1: GCV search of lambda on the normalised run; 0: lambda = fixed_lam on the raw run
+    double fixed_lam, smoothing_factor;
+};
+hipError_t p2s_launch_gcv_spline(const P2sGcvArgs &a, hipStream_t s);
+
 struct P2sMetricsArgs {
     const double *xyz;           // [n_frames][n_markers][3]
     const int32_t *bones;        // [n_bones][2] (parent, child) marker indices

@@ -219,6 +219,35 @@ class Engine:
                                                      _ptr(params) if params.size else None, params.size, _ptr(out) if out.size else None))
         return out
 
+    _GCV_ERRORS = {_lib.P2S_ERR_GCV_SHORT_RUN: ValueError, _lib.P2S_ERR_GCV_ILL_POSED: ValueError,
+                   _lib.P2S_ERR_GCV_NO_MINIMUM: ValueError, _lib.P2S_ERR_GCV_SINGULAR: np.linalg.LinAlgError}
+
+    def gcv_spline(self, data, cutoff='auto', smoothing_factor=1.0, frame_rate=None):
+        """gcv_spline_filter_1d (filtering.py:163-313) on every column of data [n_frames][n_cols]: a natural cubic
+        smoothing spline through every run of >= 5 valid samples, lambda chosen by GCV (cutoff 'auto') or
+        (frame_rate / (2 pi cutoff))^4, times smoothing_factor either way.  Returns (out, lam): the filtered matrix and
+        [n_frames][n_cols] the lambda of the fit at the first sample of every filtered run, NaN elsewhere.  Failures
+        raise what the reference raises: ValueError (a run of 2 to 4 samples, an ill-posed problem, a search without a
+        minimum, a negative lambda), numpy.linalg.LinAlgError (a singular system)."""
+        if not hasattr(self._lib, 'p2s_gcv_spline_host'):
+            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_gcv_spline_host: rebuild it')
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        if data.ndim != 2:
+            raise P2sError(f'data has shape {data.shape}; expected [n_frames][n_cols]')
+        auto = cutoff == 'auto'
+        lam = 0.0 if auto else float((frame_rate / (2 * np.pi * float(cutoff))) ** 4)     # filtering.py:301
+        out = np.empty_like(data)
+        lam_out = np.full(data.shape, np.nan)
+        p = lambda x: _ptr(x) if x.size else None                           # noqa: E731
+        rc = self._lib.p2s_gcv_spline_host(self._h, data.shape[0], data.shape[1], p(data), 1 if auto else 0, lam,
+                                           float(smoothing_factor), p(out), p(lam_out))
+        if rc in self._GCV_ERRORS:
+            raise self._GCV_ERRORS[rc](self._lib.p2s_last_error().decode())
+        if rc == _lib.P2S_ERR_INVALID_ARG and self._lib.p2s_last_error().decode() == 'Regularization parameter should be non-negative':
+            raise ValueError('Regularization parameter should be non-negative')
+        _lib.check(rc)
+        return out, lam_out
+
     def trc_metrics(self, xyz, bones):
         """trc_evaluate's per-frame quantities for xyz [F][K][3] and bones [n][2] (parent, child marker indices):
         bone_len [n][F], bone_stats [n][3] (mean, population sd, n_valid), accel [K][F-2], missing [K]."""

@@ -10,15 +10,18 @@ What runs where:
 * ``gaussian`` (:513-529) .................................................. p2s_gauss_kernel, weights from scipy's own kernel
 * ``median`` (:561-577) .................................................... p2s_median_kernel
 * ``one_euro`` (:87-160) ................................................... p2s_one_euro_kernel
+* ``gcv_spline`` (:163-313) ................................................ p2s_gcv_spline_kernel: natural cubic
+  smoothing spline of every run of >= 5 valid samples, lambda from the cut-off frequency or chosen by generalised
+  cross-validation (scipy.interpolate.make_smoothing_spline's criterion and minimize_scalar's bounded search, one lane
+  per run); the median / MAD normalisation of 'auto' is computed by the host
 
 * ``kalman`` (:316-434) .................................................... p2s_kalman_kernel -- PARITY UNPINNED: the
   reference takes the filter and the smoother from filterpy, which is not importable where this was built; the kernel
   follows filterpy's published algorithm and is checked against oracle/filtering_ref.py only
 
 Coefficients and kernel weights come from the very SciPy calls the reference makes, so the kernels reproduce its numbers
-to rounding.  ``gcv_spline`` and ``loess`` need make_smoothing_spline's private GCV search / statsmodels: they are
-refused with NotImplementedError.  The
-figures of the reference (``display_figures``, ``save_filt_plots``) are a GUI matter and not produced.
+to rounding.  ``loess`` needs statsmodels, which is not importable where this was built: it is refused with
+NotImplementedError.  The figures of the reference (``display_figures``, ``save_filt_plots``) are a GUI matter and not produced.
 """
 import glob
 import logging
@@ -29,7 +32,7 @@ import numpy as np
 from . import trc as trc_mod
 
 FILTER_HAMPEL, FILTER_GAUSSIAN, FILTER_MEDIAN, FILTER_ONE_EURO, FILTER_KALMAN = 1, 2, 3, 4, 5    # include/p2s.h
-REFUSED_TYPES = {'gcv_spline': 'scipy.interpolate.make_smoothing_spline and its GCV search', 'loess': 'statsmodels'}
+REFUSED_TYPES = {'loess': 'statsmodels'}
 
 
 def _make_engine():
@@ -104,6 +107,18 @@ def kalman_filter(data, frame_rate, trust_ratio, smooth=True, engine=None):
                                                        1.0 if int(smooth) else 0.0])
 
 
+def gcv_spline_filter(data, cutoff, smoothing_factor, frame_rate, engine=None):
+    """gcv_spline_filter_1d (filtering.py:163-313) on every column: cutoff 'auto' chooses lambda by generalised
+    cross-validation on the median/MAD-normalised run, a number gives lambda = (frame_rate / (2 pi cutoff))^4; either
+    is multiplied by smoothing_factor.  A run of 2 to 4 valid samples raises the reference's ValueError.  An engine
+    without gcv_spline (or whose library lacks the entry point) raises NotImplementedError."""
+    engine = engine or _make_engine()
+    if not hasattr(engine, 'gcv_spline'):
+        raise NotImplementedError("filter type 'gcv_spline' needs an engine with gcv_spline, which this one lacks")
+    out, _ = engine.gcv_spline(data, cutoff, float(smoothing_factor), frame_rate)
+    return out
+
+
 def _apply(filter_type, fcfg, data, frame_rate, engine):
     """filter1d (filtering.py:632-662) for a whole matrix."""
     if filter_type == 'butterworth':
@@ -122,6 +137,9 @@ def _apply(filter_type, fcfg, data, frame_rate, engine):
     if filter_type == 'kalman':
         p = fcfg.get('kalman')
         return kalman_filter(data, frame_rate, p.get('trust_ratio'), p.get('smooth'), engine)
+    if filter_type == 'gcv_spline':
+        p = _sub(fcfg, 'gcv_spline')
+        return gcv_spline_filter(data, p.get('cut_off_frequency', 'auto'), p.get('smoothing_factor', 1.0), frame_rate, engine)
     if filter_type in REFUSED_TYPES:
         raise NotImplementedError(f"filter type '{filter_type}' needs {REFUSED_TYPES[filter_type]}, which is not part of this build")
     raise KeyError(filter_type)                                # the reference's filter_mapping[filter_type]
@@ -158,6 +176,10 @@ _TYPE_LINES = {
                                        f"Cut-off frequency {int(_sub(f, 'butterworth_on_speed').get('cut_off_frequency'))} Hz."),
     'gaussian': lambda f: f"--> Filter type: Gaussian. Standard deviation kernel: {int(_sub(f, 'gaussian').get('sigma_kernel'))}",
     'median': lambda f: f"--> Filter type: Median. Kernel size: {_sub(f, 'median').get('kernel_size')}",
+    'gcv_spline': lambda f: (f"--> Filter type: Generalized Cross-Validation Spline. Optimal parameters automatically estimated with smoothing factor "
+                             f"{float(_sub(f, 'gcv_spline').get('smoothing_factor', 1.0))}."
+                             if _sub(f, 'gcv_spline').get('cut_off_frequency', 'auto') == 'auto'
+                             else "--> Filter type: Generalized Cross-Validation Spline. Cut-off frequency {gcv_filter_cutoff} Hz."),
     'kalman': lambda f: (f"--> Filter type: Kalman {'smoother' if int(_sub(f, 'kalman').get('smooth')) else 'filter'}. Measurements trusted "
                          f"{int(_sub(f, 'kalman').get('trust_ratio'))} times as much as previous data, assuming a constant acceleration process."),
 }
