@@ -245,7 +245,7 @@ int p2s_get_assoc_stats(p2s_ctx *ctx, uint64_t *out, int32_t reset);
 
 /* Experiments and tests only -- apart from P2S_TUNE_MAX_SUBSETS nothing here changes a result, and the library never
  * reads the environment.
- *   P2S_TUNE_TRI_PATH     P2S_TRI_PATH_AUTO (default): the pooled one-launch kernel (failures of three tiles pooled, fp32
+ *   P2S_TUNE_TRI_PATH     P2S_TRI_PATH_AUTO (default): the pooled one-launch kernel (failures of five tiles pooled, fp32
  *                         screen + fp64 evaluation of the surviving camera subsets) where it applies (pinhole, no L/R swap,
  *                         float32 observations, up to 16 cameras), else round 2's one-launch kernel (float64 observations,
  *                         up to 8 cameras), else the streaming + work-list search pair;

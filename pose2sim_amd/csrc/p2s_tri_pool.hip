@@ -5,11 +5,11 @@
 //   tier A (screen, fp32, two subsets per lane in packed registers): every candidate subset of a level is evaluated in
 //     single precision in coordinates centred on the unit's level-0 point -- normal matrix of the kept cameras by
 //     downdate, smallest eigenpair by two Rayleigh steps, mean reprojection error.  It decides nothing by itself: a
-//     candidate is dropped only if its fp32 error, minus a margin that is 30x the largest deviation from the fp64 error
-//     seen on any workload (exp/screen_proto.py, tests/sweeps), cannot be the level's minimum and -- on a level that is
+//     candidate is dropped only if its fp32 error, minus a margin fitted to the deviations from the fp64 error measured
+//     per rig family (exp/screen_proto.py), cannot be the level's minimum and -- on a level that is
 //     not the unit's last, so that a failed level leaves nothing behind -- cannot be under the threshold.  Candidates
 //     the screen cannot vouch for (ill-conditioned system, eigen-iteration not settled, degenerate projection, level-0
-//     point far away or not finite) always go on.
+//     point far away or not finite, a downdate that cancels) always go on.
 //   tier B (fp64): the survivors -- 0.93 per searching unit on BASELINE configs[1] instead of 8 -- of ALL the pooled
 //     units and levels are evaluated together, one per lane, by exactly the arithmetic of level 0; the argmin per unit
 //     (error, then rank: np.nanargmin's first index) goes through LDS atomics.
@@ -181,10 +181,14 @@ __device__ __forceinline__ v2f rayleighv(const Sym3v &M, v2f g0, v2f g1, v2f g2,
     return num * rcp2(den);
 }
 
-// The screen's margin and guards (exp/screen_proto.py): with det / tr^3 >= 3e-3 (condition number of M - lam I below
-// ~330), the last two eigenvalue estimates within 25 % of each other, a finite result and the level-0 point within 30 m,
-// |e32 - e64| stayed under 0.03 (0.02 px + e (1e-3 + 2 dlam)) on every candidate of every workload tried.
-constexpr float kCondMin = 3e-3f, kDlamMax = 0.25f, kMargAbs = 0.02f, kMargRel = 1e-3f, kMargDlam = 2.0f, kCentreMax2 = 900.0f;
+// The screen's margin and guards (exp/screen_proto.py): a candidate is vouched for with det / tr^3 >= 1e-2
+// for M - lam I (1/27 when its eigenvalues are equal), the last two eigenvalue estimates within 25 % of each other, a
+// finite result, the level-0 point within 30 m and the kept cameras carrying at least 1/8 of the base's trace (no
+// cancelling downdate: likelihoods of 1e-3 kept beside removed ones of 1 left |e32 - e64| at 10-300x the margin
+// otherwise); the margin is 0.02 px + e (1e-3 + 8 dlam).  With these, |e32 - e64| stayed below 0.72 of the margin on every
+// rig family and likelihood mode modelled; with det / tr^3 >= 3e-3 candidates at the edge of the guard reached 5.4x.
+constexpr float kCondMin = 1e-2f, kDlamMax = 0.25f, kMargAbs = 0.02f, kMargRel = 1e-3f, kMargDlam = 8.0f, kCentreMax2 = 900.0f;
+constexpr float kCancelMax = 8.0f;
 
 template <typename T, int CT, int NSLOT, bool EXACT, int TPW>
 __global__ void __launch_bounds__(64, P2S_POOL_WPS) p2s_tri_pool_kernel(const P2sTriArgs a) {
@@ -482,6 +486,12 @@ __global__ void __launch_bounds__(64, P2S_POOL_WPS) p2s_tri_pool_kernel(const P2
                                 return b;
                             };
                             const Base bA = downdate(goA, RA), bB = downdate(goB, RB);
+                            // the downdate cancels: the kept cameras carry less than 1 / kCancelMax of the base's trace (a
+                            // light camera kept, heavy ones removed), and fp32 rounding of the base swamps what is left.  The
+                            // downdated diagonal tells: its rounding is a few ulps of the base's, far below the bound.
+                            const float tr_lim = base.m00 + base.m11 + base.m22;
+                            const bool keptA_ok = (bA.m00 + bA.m11 + bA.m22) * kCancelMax >= tr_lim;
+                            const bool keptB_ok = (bB.m00 + bB.m11 + bB.m22) * kCancelMax >= tr_lim;
                             const Sym3v M{v2f{bA.m00, bB.m00}, v2f{bA.m01, bB.m01}, v2f{bA.m02, bB.m02}, v2f{bA.m11, bB.m11}, v2f{bA.m12, bB.m12}, v2f{bA.m22, bB.m22}};
                             const v2f g0{bA.g0, bB.g0}, g1{bA.g1, bB.g1}, g2{bA.g2, bB.g2}, h{bA.h, bB.h};
                             // smallest eigenpair of the pencil: (M - lam) q = lam c0 - g, lam = Rayleigh quotient; from
@@ -519,9 +529,9 @@ __global__ void __launch_bounds__(64, P2S_POOL_WPS) p2s_tri_pool_kernel(const P2
                             const v2f marg = fma2(e32, fma2(splat2(kMargDlam), v2f{dlamA, dlamB}, splat2(kMargRel)), splat2(kMargAbs));
                             // (every comparison is false for a NaN: anything that went wrong above leaves the candidate unvouched)
                             const bool gA = (a00.x > 0.0f) && (c22.x > 0.0f) && (det.x > 0.0f) && (nkA >= 2) && (det.x >= cond_lim.x) &&
-                                            (dlamA <= kDlamMax) && (e32.x < kInfF);
+                                            (dlamA <= kDlamMax) && (e32.x < kInfF) && keptA_ok;
                             const bool gB = (a00.y > 0.0f) && (c22.y > 0.0f) && (det.y > 0.0f) && (nkB >= 2) && (det.y >= cond_lim.y) &&
-                                            (dlamB <= kDlamMax) && (e32.y < kInfF);
+                                            (dlamB <= kDlamMax) && (e32.y < kInfF) && keptB_ok;
                             loA = gA ? e32.x - marg.x : -kInfF; hiA = gA ? e32.x + marg.x : kInfF;
                             loB = gB ? e32.y - marg.y : -kInfF; hiB = gB ? e32.y + marg.y : kInfF;
                         }

@@ -392,18 +392,23 @@ def test_pooled_search_slots_and_tile_pairing(C, p_outlier, F, singles_pct):
     ('4 cameras, weak geometry', 6_000, 4, 26, 2, False, dict(p_outlier=0.08, p_lowlik=0.10)),
     ('3 cameras', 6_000, 3, 26, 2, False, dict(p_outlier=0.10)),
     ('5 cameras x 131 keypoints', 800, 5, 131, 3, False, dict(p_outlier=0.10, p_missing_cam=0.05)),
+    ('12 cameras', 2_000, 12, 26, 3, False, dict(p_outlier=0.10, p_lowlik=0.08)),
+    ('16 cameras', 2_000, 16, 26, 2, False, dict(p_outlier=0.08, p_missing_cam=0.02)),
 ])
 @pytest.mark.parametrize('tiles', [2, 3, 4, 5, 6])
 def test_screen_changes_nothing(name, F, C, K, min_cams, f64, gen, tiles):
     """The pooled kernel's fp32 screen decides which camera subsets reach the fp64 evaluation and nothing else: with the
-    screen off (every candidate evaluated in fp64) every output bit is the same, on seven workloads and for 2, 3 and 4
-    tiles pooled per wave -- and fewer subsets were evaluated in fp64 with it on.  Every unit against the C oracle as well."""
+    screen off (every candidate evaluated in fp64) every output bit is the same, on nine workloads -- and fewer subsets were
+    evaluated in fp64 with it on.  Every unit against the C oracle as well.  The number of tiles pooled per wave (2-6)
+    selects the instantiation for 5-8 cameras only; 3-4 cameras always pool five and 9-16 cameras two, so for those the
+    parameter only varies the workload's seed (9-16 cameras: observations taken eight at a time, the slot keeps the fp64
+    normal matrix).  tests/test_tri_screen_gpu.py covers other rigs and low likelihoods."""
     import __graft_entry__ as entry
     entry.build_hip()
     from oracle import tri_oracle
     from pose2sim_amd.engine import Engine
     from pose2sim_amd import synth
-    wl = synth.make_config(F, C, K, 1, seed=900 + C + K, **gen)
+    wl = synth.make_config(F, C, K, 1, seed=900 + C + K + (tiles if C > 8 else 0), **gen)
     outs, evals = {}, {}
     for screen in (1, 0):
         eng = Engine(0)
