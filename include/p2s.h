@@ -225,6 +225,32 @@ int p2s_gcv_spline_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const do
 int p2s_trc_metrics_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_markers, const double *xyz, int32_t n_bones,
                          const int32_t *bones, double *bone_len, double *bone_stats, double *accel, int64_t *missing);
 
+/* ---- synchronization (synchronize_cams_all, synchronization.py:1346-1612) ------------------------------------------
+ * Speeds: replaces the per-camera pandas / scipy work of :1562-1584 (interpolate_zeros_nans :1565, bfill().ffill(),
+ * signal.filtfilt :1568, vert_speed :1271-1288, abs().sum(axis=1) :1579, filtfilt of the sum :1585).  coords: the cameras'
+ * [n_frames[c]][n_cols] row-major blocks back to back, the (x, y) columns of the keypoints to consider in model order with
+ * the low-likelihood triplets already NaN (convert_json2pandas, drop_col, [kpt_id_in_df]).  Per column: linear
+ * interpolation of NaN / 0 samples with extrapolation at the ends when more than 4 samples are good, bfill, ffill; then
+ * per camera with more than 3 (n_coef - 1) frames filtfilt(b, a) over every column (odd extension, padlen 3 n_coef),
+ * vertical speed = diff of the odd (y) columns, NaN -> 2x the second row's diff, sum of absolute values skipping NaN,
+ * filtfilt of that sum under the same rule.  b, a [n_coef] (a[0] = 1), zi [n_coef - 1] = scipy.signal.lfilter_zi(b, a).
+ * speeds: [sum n_frames] back to back.  Every camera needs >= 2 frames (the reference raises IndexError on 1); a camera
+ * with 3 (n_coef - 1) < n_frames <= 3 n_coef frames is refused with P2S_ERR_SYNC_PADLEN and scipy's message.  HOST
+ * pointers; blocks. */
+#define P2S_ERR_SYNC_PADLEN (-10)
+int p2s_sync_speeds_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, int32_t n_cols, const double *coords,
+                         int32_t n_coef, const double *b, const double *a, const double *zi, double *speeds);
+/* Lagged Pearson: replaces time_lagged_cross_corr (synchronization.py:1291-1343) for n_sig compared signals at once.
+ * For signal s (sig_len[s] samples, back to back in sig) and lag l in [lag_lo, lag_hi):
+ * r[s][l - lag_lo] = Series(ref).corr(Series(sig_s).shift(l)): the pairs (ref[i], sig_s[i - l]) with
+ * i < min(n_ref, sig_len[s]), 0 <= i - l < sig_len[s], both values not NaN; np.corrcoef of them (two passes, clipped to
+ * [-1, 1]); NaN with fewer than 2 pairs or a zero variance.  argmax[s] = np.argmax(r[s]) (the first maximum, or the
+ * first NaN when there is one), max_corr[s] = np.nanmax(r[s]) (NaN when every r is NaN: the caller applies the
+ * reference's offset 0 / correlation 0).  HOST pointers; blocks. */
+int p2s_lagged_pearson_host(p2s_ctx *ctx, const double *ref, int64_t n_ref, int32_t n_sig, const double *sig,
+                            const int64_t *sig_len, int64_t lag_lo, int64_t lag_hi, double *r, int64_t *argmax,
+                            double *max_corr);
+
 /* Counters of the triangulation calls of this context since creation (or the last reset), after synchronising its
  * streams; out holds 8 values: out[0] units that entered the camera-subset search (triangulation.py:408 beyond the
  * first pass), out[1] camera subsets evaluated, out[2] 64-lane evaluation passes, out[3] units whose search stopped at
@@ -337,6 +363,21 @@ int p2s_json_gather_keypoints(const p2s_json_batch *batch, const int32_t *keypoi
  * (NaN-padded), out [n_rows][n_values]. */
 int p2s_json_gather_people(const p2s_json_batch *batch, const int64_t *file_index, const int32_t *person_index,
                            int64_t n_rows, int32_t n_values, int32_t dtype, void *out, int64_t *n_inexact);
+
+/* convert_json2pandas (synchronization.py:1185-1250, synchronization_gui false) for every file at once: in file i, the
+ * person with the largest bounding-box area over the model's keypoints (keypoint_ids, (0, 0) points included; ties and
+ * NaN as np.argmax: the first maximum, or the first NaN); then out[i][k] = (x, y, likelihood) of keypoint_ids[k] of that
+ * person, (NaN, NaN, NaN) unless likelihood > threshold.  A file on which the reference's try block raises gets NaN
+ * throughout: unreadable, no "people" list, no person, any person without a "pose_keypoints_2d" list of numbers (the
+ * reference's comprehension indexes it before its `in` test, :1219-1224), any person's list too short for a model
+ * keypoint's triplet.  JSON null reads as NaN.  out [n_files][n_ids][3] float64. */
+int p2s_json_gather_largest_person(const p2s_json_batch *batch, const int32_t *keypoint_ids, int32_t n_ids,
+                                   double likelihood_threshold, double *out);
+/* shutil.copy for n_files (source, destination) pairs on host threads: the bytes, then the source's permission bits.
+ * Paths as in p2s_json_parse.  ok [n_files] (may be NULL): 1 = copied, 0 = failed; the call then returns
+ * P2S_ERR_INVALID_ARG with the first failure's path and errno text in p2s_last_error(). */
+int p2s_copy_files(const char *src_paths, const int64_t *src_offsets, const char *dst_paths, const int64_t *dst_offsets,
+                   int64_t n_files, int32_t n_threads, int8_t *ok);
 
 /* ---- .trc data rows (host threads) ---------------------------------------------------------------------------
  * Replaces DataFrame.to_csv in make_trc (triangulation.py:214): appends n_rows lines

@@ -1,13 +1,14 @@
-"""Entry points with the reference's call signatures for the two stages this engine covers:
+"""Entry points with the reference's call signatures for the stages this engine covers:
 
     from pose2sim_amd import Pose2Sim
+    Pose2Sim.synchronization(config)        # reference: Pose2Sim.py:374-376
     Pose2Sim.personAssociation(config)      # reference: Pose2Sim.py:382-384
     Pose2Sim.triangulation(config)          # reference: Pose2Sim.py:386-388
 
 ``config`` is None (current directory), a path to a trial / session directory holding Config.toml
-files, or an already-merged config dict (Pose2Sim.py:114-162).  The other pipeline stages
-(calibration, pose estimation, synchronization, filtering, marker augmentation, kinematics) are
-outside this engine's scope and are not provided: run them with the reference.
+files, or an already-merged config dict (Pose2Sim.py:114-162).  Filtering is provided too (see filtering()).  The
+other pipeline stages (calibration, pose estimation, marker augmentation, kinematics) are outside this engine's scope
+and are not provided: run them with the reference.
 """
 import logging
 import logging.handlers
@@ -20,11 +21,12 @@ import tomli
 
 # stage name -> (headline of the log banner, module, function, name used in the "... took" line)
 _STAGES = {
+    'synchronization': ('Camera synchronization', 'synchronization', 'synchronize_cams_all', 'Synchronization'),
     'personAssociation': ('Associating persons', 'personAssociation', 'associate_all', 'Associating persons'),
     'triangulation': ('Triangulation of 2D points', 'triangulation', 'triangulate_all', 'Triangulation'),
     'filtering': ('Filtering 3D coordinates', 'filtering', 'filter_all', 'Filtering'),
 }
-_OUT_OF_SCOPE = ('calibration', 'poseEstimation', 'synchronization', 'markerAugmentation', 'kinematics', 'runAll')
+_OUT_OF_SCOPE = ('calibration', 'poseEstimation', 'markerAugmentation', 'kinematics', 'runAll')
 
 
 def _load_toml(path):
@@ -133,6 +135,12 @@ def _run_stage(name, config):
         start = time.time()
         run(config_dict)
         logging.info(f'\n{done} took {time.strftime("%Hh%Mm%Ss", time.gmtime(time.time() - start))}.\n')
+
+
+def synchronization(config=None):
+    """Synchronization of the cameras' JSON files (synchronization.synchronize_cams_all) into pose-sync/; the interactive
+    person picker (synchronization_gui = true) is refused with NotImplementedError."""
+    _run_stage('synchronization', config)
 
 
 def personAssociation(config=None):

@@ -18,6 +18,7 @@ P2S_JSON_UNREADABLE, P2S_JSON_NO_PEOPLE_LIST = -1, -2
 P2S_ERR_INVALID_ARG = -1
 P2S_ERR_GCV_SHORT_RUN, P2S_ERR_GCV_ILL_POSED, P2S_ERR_GCV_NO_MINIMUM, P2S_ERR_GCV_SINGULAR = -6, -7, -8, -9
 P2S_JSON_PERSON_NO_LIST, P2S_JSON_PERSON_NOT_NUMERIC = -1, -2
+P2S_ERR_SYNC_PADLEN = -10
 
 
 class TriParams(C.Structure):
@@ -74,6 +75,10 @@ SIGNATURES = {
     'p2s_butterworth_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'p2s_filter_columns_host': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     'p2s_gcv_spline_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    'p2s_sync_speeds_host': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    'p2s_lagged_pearson_host': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'p2s_trc_metrics_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'p2s_timing_begin': (C.c_int, [C.c_void_p]),
     'p2s_timing_end': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
@@ -83,6 +88,8 @@ SIGNATURES = {
     'p2s_json_person_lengths': (C.c_int, [C.c_void_p, C.c_void_p]),
     'p2s_json_gather_keypoints': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                             C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
+    'p2s_json_gather_largest_person': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]),
+    'p2s_copy_files': (C.c_int, [C.c_char_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     'p2s_json_gather_people': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                          C.c_void_p, C.POINTER(C.c_int64)]),
     'p2s_assoc_argmax_rows': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
@@ -97,7 +104,8 @@ SIGNATURES = {
 }
 
 # entry points a library built before them lacks (P2S_LIB may name one): left unbound, and the feature is refused
-OPTIONAL = {'p2s_gcv_spline_host'}
+OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_host', 'p2s_json_gather_largest_person',
+            'p2s_copy_files'}
 
 _lib = None
 

@@ -1011,6 +1011,93 @@ int p2s_gcv_spline_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const do
     return P2S_OK;
 }
 
+int p2s_sync_speeds_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, int32_t n_cols, const double *coords,
+                         int32_t n_coef, const double *b, const double *a, const double *zi, double *speeds) {
+    if (!ctx) return fail(P2S_ERR_INVALID_ARG, "null context");
+    if (n_cams < 0 || n_cols < 0 || (n_cols & 1)) return fail(P2S_ERR_INVALID_ARG, "bad shape: n_cams=%d n_cols=%d (x, y pairs)", n_cams, n_cols);
+    if (n_coef < 2 || n_coef > P2S_MAX_FILTER_ORDER + 1)
+        return fail(P2S_ERR_INVALID_ARG, "filter with %d coefficients: supported 2..%d", n_coef, P2S_MAX_FILTER_ORDER + 1);
+    if (n_cams == 0) return P2S_OK;
+    if (!n_frames || !b || !a || !zi || !speeds) return fail(P2S_ERR_INVALID_ARG, "null pointer");
+    if (!(a[0] == 1.0)) return fail(P2S_ERR_INVALID_ARG, "a[0] must be 1 (scipy.signal.butter normalises it)");
+    P2sSyncArgs f{};
+    f.n_cams = n_cams; f.n_cols = n_cols; f.n_order = n_coef - 1;
+    f.padlen = 3 * n_coef;                                   // scipy.signal.filtfilt's default
+    f.filter_above = 3 * (n_coef - 1);                       // synchronization.py:1539, 1567, 1584
+    for (int i = 0; i < n_coef; ++i) { f.b[i] = b[i]; f.a[i] = a[i]; }
+    for (int i = 0; i < n_coef - 1; ++i) f.zi[i] = zi[i];
+    std::vector<int64_t> row0((size_t)n_cams + 1, 0);
+    for (int c = 0; c < n_cams; ++c) {
+        const int64_t L = n_frames[c];
+        if (L < 2 || L > ((int64_t)1 << 31)) return fail(P2S_ERR_INVALID_ARG, "camera %d: %lld frames (2 .. 2^31 supported)", c, (long long)L);
+        if (L > f.filter_above && L <= f.padlen)
+            return fail(P2S_ERR_SYNC_PADLEN, "The length of the input vector x must be greater than padlen, which is %d.", f.padlen);
+        row0[(size_t)c + 1] = row0[(size_t)c] + L;
+    }
+    const int64_t rows = row0[(size_t)n_cams];
+    if (n_cols > 0 && !coords) return fail(P2S_ERR_INVALID_ARG, "null coords");
+    f.total_rows = rows;
+    const int64_t wrows = rows + (int64_t)2 * f.padlen * n_cams;
+    const size_t cbytes = (size_t)rows * n_cols * sizeof(double), wbytes = (size_t)wrows * n_cols * sizeof(double);
+    const size_t s_off = 0, sw_off = (size_t)rows * sizeof(double), r0_off = sw_off + (size_t)wrows * sizeof(double);
+    const size_t abytes = r0_off + row0.size() * sizeof(int64_t);
+    int rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = ctx->in.ensure(cbytes + 16)) != P2S_OK) return rc;
+    if ((rc = ctx->q.ensure(cbytes + 16)) != P2S_OK) return rc;
+    if ((rc = ctx->aux0.ensure(wbytes + 16)) != P2S_OK) return rc;
+    if ((rc = ctx->aux1.ensure(abytes)) != P2S_OK) return rc;
+    char *aux = (char *)ctx->aux1.p;
+    f.coords = (const double *)ctx->in.p; f.filled = (double *)ctx->q.p; f.work = (double *)ctx->aux0.p;
+    f.speed = (double *)(aux + s_off); f.speed_work = (double *)(aux + sw_off); f.row0 = (const int64_t *)(aux + r0_off);
+    if (cbytes) HIP_TRY(hipMemcpyAsync(ctx->in.p, coords, cbytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(aux + r0_off, row0.data(), row0.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(p2s_launch_sync_speeds(f, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(speeds, aux + s_off, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return P2S_OK;
+}
+
+int p2s_lagged_pearson_host(p2s_ctx *ctx, const double *ref, int64_t n_ref, int32_t n_sig, const double *sig,
+                            const int64_t *sig_len, int64_t lag_lo, int64_t lag_hi, double *r, int64_t *argmax,
+                            double *max_corr) {
+    if (!ctx) return fail(P2S_ERR_INVALID_ARG, "null context");
+    if (n_ref < 0 || n_sig < 0 || n_ref > ((int64_t)1 << 31)) return fail(P2S_ERR_INVALID_ARG, "bad shape: n_ref=%lld n_sig=%d", (long long)n_ref, n_sig);
+    if (lag_hi <= lag_lo || lag_hi - lag_lo > ((int64_t)1 << 31) || lag_lo < -((int64_t)1 << 40) || lag_hi > ((int64_t)1 << 40))
+        return fail(P2S_ERR_INVALID_ARG, "empty or too large lag range [%lld, %lld)", (long long)lag_lo, (long long)lag_hi);
+    if (n_sig == 0) return P2S_OK;
+    if (!sig_len || !r || !argmax || !max_corr || (n_ref > 0 && !ref)) return fail(P2S_ERR_INVALID_ARG, "null pointer");
+    std::vector<int64_t> sig0((size_t)n_sig + 1, 0);
+    for (int i = 0; i < n_sig; ++i) {
+        if (sig_len[i] < 0 || sig_len[i] > ((int64_t)1 << 31)) return fail(P2S_ERR_INVALID_ARG, "signal %d: bad length", i);
+        sig0[(size_t)i + 1] = sig0[(size_t)i] + sig_len[i];
+    }
+    const int64_t total = sig0[(size_t)n_sig];
+    if (total > 0 && !sig) return fail(P2S_ERR_INVALID_ARG, "null signals");
+    P2sPearsonArgs p{};
+    p.n_ref = n_ref; p.lag_lo = lag_lo; p.n_lags = lag_hi - lag_lo; p.n_sig = n_sig;
+    const size_t ref_off = 0, sig_off = (size_t)(n_ref + 1) * sizeof(double), s0_off = sig_off + (size_t)(total + 1) * sizeof(double);
+    const size_t in_bytes = s0_off + sig0.size() * sizeof(int64_t);
+    const size_t r_bytes = (size_t)n_sig * p.n_lags * sizeof(double);
+    int rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = ctx->in.ensure(in_bytes)) != P2S_OK) return rc;
+    if ((rc = ctx->q.ensure(r_bytes)) != P2S_OK) return rc;
+    if ((rc = ctx->aux0.ensure((size_t)n_sig * 16)) != P2S_OK) return rc;
+    char *in = (char *)ctx->in.p;
+    p.ref = (const double *)(in + ref_off); p.sig = (const double *)(in + sig_off); p.sig0 = (const int64_t *)(in + s0_off);
+    p.r = (double *)ctx->q.p; p.argmax = (int64_t *)ctx->aux0.p; p.max_corr = (double *)((char *)ctx->aux0.p + (size_t)n_sig * 8);
+    if (n_ref) HIP_TRY(hipMemcpyAsync(in + ref_off, ref, (size_t)n_ref * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (total) HIP_TRY(hipMemcpyAsync(in + sig_off, sig, (size_t)total * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(in + s0_off, sig0.data(), sig0.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(p2s_launch_pearson(p, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(r, p.r, r_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(argmax, p.argmax, (size_t)n_sig * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(max_corr, p.max_corr, (size_t)n_sig * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return P2S_OK;
+}
+
 int p2s_trc_metrics_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_markers, const double *xyz, int32_t n_bones,
                          const int32_t *bones, double *bone_len, double *bone_stats, double *accel, int64_t *missing) {
     if (!ctx) return fail(P2S_ERR_INVALID_ARG, "null context");

@@ -18,23 +18,11 @@
 #include <math.h>
 
 #include "p2s_internal.h"
+#include "p2s_iir.h"
 
 namespace {
 
 __device__ __forceinline__ bool sample_valid(double v) { return (v == v) && (v != 0.0); }
-
-// One sample of scipy's lfilter (direct form II transposed, a[0] = 1): y = z[0] + b[0] x, then
-// z[k] = z[k+1] + b[k+1] x - a[k+1] y.  Same operation order as scipy's C loop and no contraction, so that the result
-// matches scipy.signal.filtfilt to rounding.
-template <int N>
-__device__ __forceinline__ double iir_step(const P2sFilterArgs &a, double (&z)[N], double x) {
-#pragma clang fp contract(off)
-    const double y = z[0] + a.b[0] * x;
-#pragma unroll
-    for (int k = 0; k < N - 1; ++k) z[k] = (z[k + 1] + x * a.b[k + 1]) - y * a.a[k + 1];
-    z[N - 1] = x * a.b[N] - y * a.a[N];
-    return y;
-}
 
 template <int N>
 __global__ void __launch_bounds__(64) p2s_butter_kernel(const P2sFilterArgs a) {
@@ -70,12 +58,12 @@ __global__ void __launch_bounds__(64) p2s_butter_kernel(const P2sFilterArgs a) {
         const double e0 = ext(0);
 #pragma unroll
         for (int k = 0; k < N; ++k) z[k] = a.zi[k] * e0;
-        for (int64_t i = 0; i < E; ++i) work[i * S] = iir_step<N>(a, z, ext(i));
+        for (int64_t i = 0; i < E; ++i) work[i * S] = iir_step<N>(a.b, a.a, z, ext(i));
         const double y0 = work[(E - 1) * S];
 #pragma unroll
         for (int k = 0; k < N; ++k) z[k] = a.zi[k] * y0;
         for (int64_t i = E - 1; i >= 0; --i) {
-            const double y = iir_step<N>(a, z, work[i * S]);
+            const double y = iir_step<N>(a.b, a.a, z, work[i * S]);
             if (i >= pad && i < pad + L) out[(f + i - pad) * S] = y;
         }
         f = r;

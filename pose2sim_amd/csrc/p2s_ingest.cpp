@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 
+#include <errno.h>
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -35,7 +36,9 @@ constexpr int kMaxDepth = 256;
 enum PersonStatus : int8_t {
     kPersonOk = 0,        // object with a "pose_keypoints_2d" array of numbers
     kPersonNoList = 1,    // not an object, key missing, or the value is not an array
-    kPersonNonNumeric = 2 // array holding something that is not a number / null / bool
+    kPersonNonNumeric = 2, // array holding something that is not a number / null / bool
+    kPersonBadList = 3    // object whose "pose_keypoints_2d" is not an array (read as kPersonNoList except by the
+                          // synchronization gather: indexing that value raises in the reference)
 };
 
 struct Person {
@@ -250,7 +253,7 @@ struct Parser {
         ws();
         if (p >= end) return fail();
         if (*p != '[') {
-            person.status = kPersonNoList;
+            person.status = kPersonBadList;
             person.len = 0;
             return skip(3);
         }
@@ -602,7 +605,7 @@ int p2s_json_person_lengths(const p2s_json_batch *b, int32_t *lengths) {
         for (int32_t n = 0; n < fr.count; ++n) {
             const Person &ps = arena.persons[(size_t)(fr.first_person + n)];
             lengths[b->person_base[(size_t)i] + n] =
-                ps.status == kPersonOk ? ps.len : (ps.status == kPersonNoList ? P2S_JSON_PERSON_NO_LIST : P2S_JSON_PERSON_NOT_NUMERIC);
+                ps.status == kPersonOk ? ps.len : (ps.status == kPersonNoList || ps.status == kPersonBadList ? P2S_JSON_PERSON_NO_LIST : P2S_JSON_PERSON_NOT_NUMERIC);
         }
     }
     return P2S_OK;
@@ -676,6 +679,72 @@ int64_t gather_people(const p2s_json_batch *b, const int64_t *file_of, const int
     return inexact_total.load();
 }
 
+
+// convert_json2pandas (synchronization.py:1185-1250) on one parsed file; false where the reference's try block raises.
+bool largest_person(const p2s_json_batch *b, int64_t i, const int32_t *ids, int32_t n_ids, double thr, double *dst) {
+    const FileRec &fr = b->files[(size_t)i];
+    if (fr.count <= 0) return false;                                  // no "people" list / np.argmax of an empty list
+    const Arena &arena = b->arenas[(size_t)fr.thread];
+    int32_t best = -1;
+    double best_area = 0.0;
+    for (int32_t n = 0; n < fr.count; ++n) {
+        // the comprehension of :1219-1224 indexes p['pose_keypoints_2d'] before its `in p` test: a person without a
+        // list of numbers (or not an object) raises, whatever its place
+        const Person &ps = arena.persons[(size_t)(fr.first_person + n)];
+        if (ps.status != kPersonOk || n_ids == 0) return false;      // (no keypoint: max() of an empty array)
+        const double *v = arena.values.data() + ps.off;
+        double x_lo = 0, x_hi = 0, y_lo = 0, y_hi = 0;
+        bool nan = false;
+        for (int32_t k = 0; k < n_ids; ++k) {
+            const int64_t j = (int64_t)ids[k] * 3;
+            if (ids[k] < 0 || j + 2 >= ps.len) return false;          // a short slice: ragged array / IndexError
+            const double x = v[j], y = v[j + 1];
+            if (x != x || y != y) nan = true;
+            if (k == 0) { x_lo = x_hi = x; y_lo = y_hi = y; }
+            x_lo = std::fmin(x_lo, x); x_hi = std::fmax(x_hi, x); y_lo = std::fmin(y_lo, y); y_hi = std::fmax(y_hi, y);
+        }
+        const double area = nan ? std::numeric_limits<double>::quiet_NaN() : (x_hi - x_lo) * (y_hi - y_lo);
+        if (best < 0) { best = n; best_area = area; continue; }       // np.argmax: the first NaN, else the first maximum
+        if (best_area != best_area) continue;
+        if (area != area || area > best_area) { best = n; best_area = area; }
+    }
+    const Person &chosen = arena.persons[(size_t)(fr.first_person + best)];
+    const double *v = arena.values.data() + chosen.off;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int32_t k = 0; k < n_ids; ++k) {
+        const int64_t j = (int64_t)ids[k] * 3;
+        const bool keep = v[j + 2] > thr;                             // j[2] > likelihood_threshold
+        dst[3 * k + 0] = keep ? v[j + 0] : nan;
+        dst[3 * k + 1] = keep ? v[j + 1] : nan;
+        dst[3 * k + 2] = keep ? v[j + 2] : nan;
+    }
+    return true;
+}
+
+bool copy_one(const std::string &src, const std::string &dst, std::vector<char> &buf, int &err) {
+    const int in = open(src.c_str(), O_RDONLY | O_CLOEXEC);
+    if (in < 0) { err = errno; return false; }
+    struct stat st;
+    if (fstat(in, &st) != 0) { err = errno; close(in); return false; }
+    const int out = open(dst.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+    if (out < 0) { err = errno; close(in); return false; }
+    if (buf.size() < (1 << 16)) buf.resize(1 << 16);
+    bool ok = true;
+    while (ok) {
+        const ssize_t r = read(in, buf.data(), buf.size());
+        if (r < 0) { err = errno; ok = false; break; }
+        if (r == 0) break;
+        for (ssize_t w = 0; w < r;) {
+            const ssize_t k = write(out, buf.data() + w, (size_t)(r - w));
+            if (k < 0) { err = errno; ok = false; break; }
+            w += k;
+        }
+    }
+    close(in);
+    if (close(out) != 0 && ok) { err = errno; ok = false; }
+    if (ok && chmod(dst.c_str(), st.st_mode & 07777) != 0) { err = errno; ok = false; }   // shutil.copymode
+    return ok;
+}
 }  // namespace
 
 extern "C" {
@@ -710,6 +779,52 @@ int p2s_json_gather_people(const p2s_json_batch *b, const int64_t *file_index, c
     const int64_t bad = dtype == P2S_F32 ? gather_people<float>(b, file_index, person_index, n_rows, n_values, (float *)out)
                                          : gather_people<double>(b, file_index, person_index, n_rows, n_values, (double *)out);
     if (n_inexact) *n_inexact = bad;
+    return P2S_OK;
+}
+
+int p2s_json_gather_largest_person(const p2s_json_batch *b, const int32_t *keypoint_ids, int32_t n_ids,
+                                   double likelihood_threshold, double *out) {
+    if (!b || (n_ids > 0 && !keypoint_ids) || (b->n_files > 0 && n_ids > 0 && !out))
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
+    if (n_ids < 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "negative size");
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    parallel_for(b->n_files, pick_threads(b->n_threads, b->n_files / 256 + 1), 256, [&](int, int64_t lo, int64_t hi) {
+        for (int64_t i = lo; i < hi; ++i) {
+            double *dst = out + i * (int64_t)n_ids * 3;
+            if (!largest_person(b, i, keypoint_ids, n_ids, likelihood_threshold, dst))
+                for (int64_t k = 0; k < (int64_t)n_ids * 3; ++k) dst[k] = nan;   // the except branch: all NaN
+        }
+    });
+    return P2S_OK;
+}
+
+int p2s_copy_files(const char *src_paths, const int64_t *src_offsets, const char *dst_paths, const int64_t *dst_offsets,
+                   int64_t n_files, int32_t n_threads, int8_t *ok) {
+    if (n_files < 0 || (n_files > 0 && (!src_paths || !src_offsets || !dst_paths || !dst_offsets)))
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "bad path table");
+    std::atomic<int64_t> first_bad{n_files};
+    std::vector<int> errs((size_t)n_files, 0);
+    parallel_for(n_files, pick_threads(n_threads, n_files / 64 + 1), 64, [&](int, int64_t lo, int64_t hi) {
+        std::vector<char> buf;
+        std::string src, dst;
+        for (int64_t i = lo; i < hi; ++i) {
+            src.assign(src_paths + src_offsets[i], (size_t)(src_offsets[i + 1] - src_offsets[i]));
+            dst.assign(dst_paths + dst_offsets[i], (size_t)(dst_offsets[i + 1] - dst_offsets[i]));
+            int err = 0;
+            const bool done = copy_one(src, dst, buf, err);
+            if (ok) ok[i] = done ? 1 : 0;
+            if (!done) {
+                errs[(size_t)i] = err;
+                int64_t cur = first_bad.load();
+                while (i < cur && !first_bad.compare_exchange_weak(cur, i)) {}
+            }
+        }
+    });
+    const int64_t bad = first_bad.load();
+    if (bad < n_files) {
+        const std::string src(src_paths + src_offsets[bad], (size_t)(src_offsets[bad + 1] - src_offsets[bad]));
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "copy of %s failed: %s", src.c_str(), strerror(errs[(size_t)bad]));
+    }
     return P2S_OK;
 }
 

@@ -214,6 +214,33 @@ struct P2sGcvArgs {
 };
 hipError_t p2s_launch_gcv_spline(const P2sGcvArgs &a, hipStream_t s);
 
+// p2s_sync.hip: synchronization speeds and their time-lagged Pearson correlation (synchronization.py:1271-1343, 1541-1575)
+struct P2sSyncArgs {
+    const double *coords;        // [total_rows][n_cols]: the cameras' masked (x, y) columns back to back
+    double *filled;              // [total_rows][n_cols]: interpolated, filled and filtered columns
+    double *work;                // [total_rows + 2 padlen n_cams][n_cols]: forward passes (camera c from row row0[c] + 2 padlen c)
+    double *speed;               // [total_rows]: sum of |vertical speeds|, then filtered in place
+    double *speed_work;          // [total_rows + 2 padlen n_cams]
+    const int64_t *row0;         // [n_cams + 1] first row of each camera
+    int64_t total_rows;
+    int32_t n_cams, n_cols, n_order, padlen;   // n_order = len(b) - 1; padlen = 3 len(b) (scipy's filtfilt)
+    int32_t filter_above;        // a camera is filtered when it has more frames than this (3 n_order, :1567)
+    double b[P2S_MAX_FILTER_ORDER + 1], a[P2S_MAX_FILTER_ORDER + 1], zi[P2S_MAX_FILTER_ORDER];
+};
+hipError_t p2s_launch_sync_speeds(const P2sSyncArgs &a, hipStream_t s);
+
+struct P2sPearsonArgs {
+    const double *ref;           // [n_ref]
+    const double *sig;           // the compared signals back to back
+    const int64_t *sig0;         // [n_sig + 1] offsets into sig
+    double *r;                   // [n_sig][n_lags]: r of lag lag_lo + t
+    int64_t *argmax;             // [n_sig]
+    double *max_corr;            // [n_sig]
+    int64_t n_ref, lag_lo, n_lags;
+    int32_t n_sig;
+};
+hipError_t p2s_launch_pearson(const P2sPearsonArgs &a, hipStream_t s);
+
 struct P2sMetricsArgs {
     const double *xyz;           // [n_frames][n_markers][3]
     const int32_t *bones;        // [n_bones][2] (parent, child) marker indices

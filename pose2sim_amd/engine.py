@@ -265,6 +265,52 @@ class Engine:
         _lib.check(self._lib.p2s_trc_metrics_host(self._h, F, K, p(xyz), nb, p(bones), p(bone_len), p(bone_stats), p(accel), p(missing)))
         return bone_len, bone_stats, accel, missing
 
+    # -- synchronization (synchronization.py:1271-1343, 1541-1585) -------------------------------------------------------
+    def sync_speeds(self, coords, b, a, zi):
+        """coords: one [n_frames][n_cols] array per camera, the (x, y) columns of the keypoints to consider with the
+        low-likelihood points NaN.  Interpolation, bfill / ffill, zero-phase Butterworth filter of every column (cameras
+        with more than 3 (len(b) - 1) frames), sum of |vertical speed|, filter of that sum.  -> one speed array per
+        camera.  A camera whose length lies between the reference's threshold and scipy's padlen raises scipy's
+        ValueError."""
+        if not hasattr(self._lib, 'p2s_sync_speeds_host'):
+            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_sync_speeds_host: rebuild it')
+        cols = [np.ascontiguousarray(c, dtype=np.float64) for c in coords]
+        if any(c.ndim != 2 for c in cols) or len({c.shape[1] for c in cols}) > 1:
+            raise P2sError('every camera needs an [n_frames][n_cols] array with the same n_cols')
+        n_cols = cols[0].shape[1] if cols else 0
+        lens = np.array([c.shape[0] for c in cols], dtype=np.int64)
+        flat = np.ascontiguousarray(np.concatenate([c.reshape(-1) for c in cols])) if cols else np.zeros(0)
+        b = np.ascontiguousarray(b, dtype=np.float64); a = np.ascontiguousarray(a, dtype=np.float64)
+        zi = np.ascontiguousarray(zi, dtype=np.float64)
+        if len(a) != len(b) or len(zi) != len(b) - 1:
+            raise P2sError('b, a and zi must have n, n and n - 1 coefficients')
+        out = np.empty(int(lens.sum()), dtype=np.float64)
+        p = lambda x: _ptr(x) if x.size else None                           # noqa: E731
+        rc = self._lib.p2s_sync_speeds_host(self._h, len(cols), p(lens), n_cols, p(flat), len(b), _ptr(b), _ptr(a),
+                                            _ptr(zi), p(out))
+        if rc == _lib.P2S_ERR_SYNC_PADLEN:
+            raise ValueError(self._lib.p2s_last_error().decode())
+        _lib.check(rc)
+        return np.split(out, np.cumsum(lens)[:-1]) if cols else []
+
+    def lagged_pearson(self, ref, signals, lag_lo, lag_hi):
+        """Series(ref).corr(Series(s).shift(lag)) for every signal s and lag in [lag_lo, lag_hi).
+        -> (r [n_sig][n_lags], argmax [n_sig] as np.argmax of each r row, max_corr [n_sig] as np.nanmax)."""
+        if not hasattr(self._lib, 'p2s_lagged_pearson_host'):
+            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_lagged_pearson_host: rebuild it')
+        ref = np.ascontiguousarray(ref, dtype=np.float64).reshape(-1)
+        sigs = [np.ascontiguousarray(s, dtype=np.float64).reshape(-1) for s in signals]
+        lens = np.array([len(s) for s in sigs], dtype=np.int64)
+        flat = np.ascontiguousarray(np.concatenate(sigs)) if sigs else np.zeros(0)
+        n_lags = int(lag_hi) - int(lag_lo)
+        r = np.empty((len(sigs), max(n_lags, 0)), dtype=np.float64)
+        arg = np.zeros(len(sigs), dtype=np.int64)
+        mx = np.full(len(sigs), np.nan)
+        p = lambda x: _ptr(x) if x.size else None                           # noqa: E731
+        _lib.check(self._lib.p2s_lagged_pearson_host(self._h, p(ref), len(ref), len(sigs), p(flat), p(lens), int(lag_lo),
+                                                     int(lag_hi), p(r), p(arg), p(mx)))
+        return r, arg, mx
+
     # -- association -----------------------------------------------------------------------
     @staticmethod
     def assoc_params(recon_thr, min_affinity, min_cams, max_iter=20, w_rank=50.0, tol=1e-4, w_sparse=0.1):

@@ -90,3 +90,26 @@ class JsonBatch:
                                                     int(n_values), P2S_F32 if out.dtype == np.float32 else P2S_F64,
                                                     _ptr(out), C.byref(bad)))
         return out, bad.value
+
+    def gather_largest_person(self, keypoint_ids, likelihood_threshold):
+        """convert_json2pandas (synchronization.py:1185-1250) for every file: (x, y, likelihood) [n_files][n_ids][3] of
+        the person with the largest bounding box, NaN below the threshold or where the reference's try block raises."""
+        ids = np.ascontiguousarray(keypoint_ids, dtype=np.int32)
+        out = np.empty((self.n_files, len(ids), 3), dtype=np.float64)
+        _lib.check(self._lib.p2s_json_gather_largest_person(self._h, _ptr(ids), len(ids), float(likelihood_threshold),
+                                                            _ptr(out)))
+        return out
+
+
+def copy_files(pairs, n_threads=0):
+    """shutil.copy(src, dst) for every (src, dst) pair on host threads (p2s_copy_files); raises OSError on a failure."""
+    lib = _lib.load()
+    enc_s = [s.encode() for s, _ in pairs]
+    enc_d = [d.encode() for _, d in pairs]
+    off_s = np.zeros(len(pairs) + 1, dtype=np.int64); off_d = np.zeros(len(pairs) + 1, dtype=np.int64)
+    if pairs:
+        np.cumsum([len(e) for e in enc_s], out=off_s[1:]); np.cumsum([len(e) for e in enc_d], out=off_d[1:])
+    rc = lib.p2s_copy_files(b''.join(enc_s), off_s.ctypes.data_as(C.c_void_p), b''.join(enc_d), off_d.ctypes.data_as(C.c_void_p),
+                            len(pairs), int(n_threads), None)
+    if rc != 0:
+        raise OSError(lib.p2s_last_error().decode())
