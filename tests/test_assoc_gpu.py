@@ -106,33 +106,33 @@ def test_edge_frames(engine):
             assert np.abs(aff[f, :N, :N] - ref).max() <= 1e-9
 
 
-@pytest.mark.parametrize('max_iter', [20, 3])
-def test_every_matrix_order(engine, max_iter):
-    """Frames of 1 .. 40 detections (odd and even orders, empty cameras, one frame per order): the symmetric one-wave
-    kernel up to 32 -- its 16-row form when the largest frame of a call has at most 16 -- and the general kernel
-    above, against the oracle; converged result and the continuous iterate after 3 passes."""
+def _every_order(engine, max_iter, f64):
     from oracle import association_ref as ar
-    C, Pn, Kj = 10, 4, 26
+    from pose2sim_amd.engine import P2S_F32, P2S_F64, as_packed
+    C, Pn, Kj = 10, 5, 26
     cams = synth.make_cameras(C, seed=21)
     P = synth.projection_matrices(cams)
-    xyl = synth.make_observations(synth.make_points3d(40, Pn, Kj, seed=22), cams, seed=22, p_missing_cam=0.0, p_outlier=0.0)   # [F][Pn][C][K][3]
+    xyl = synth.make_observations(synth.make_points3d(48, Pn, Kj, seed=22), cams, seed=22, p_missing_cam=0.0, p_outlier=0.0)   # [F][Pn][C][K][3]
     cal = {'inv_K': cams['inv_K'], 'R_mat': cams['R_mat'], 'T': cams['T']}
     rng = np.random.default_rng(23)
     frames = []
-    for total in range(1, 41):
+    for total in range(1, 49):
         counts = np.zeros(C, dtype=int)
         for _ in range(total):                            # spread `total` detections over the cameras, at most Pn each
             c = rng.choice(np.flatnonzero(counts < Pn))
             counts[c] += 1
-        frames.append([[np.nan_to_num(xyl[total - 1, p, c]).astype(np.float32).astype(np.float64).ravel()
+        # float64: the float32 numbers shifted off the float32 grid, the oracle reads the same
+        frames.append([[(np.nan_to_num(xyl[total - 1, p, c]).astype(np.float32).astype(np.float64) + (1e-9 if f64 else 0.0)).ravel()
                         for p in rng.permutation(Pn)[:counts[c]]] for c in range(C)])
     engine.set_calibration(P, cams)
     min_aff = 0.2 if max_iter == 20 else -1.0
     prm = engine.assoc_params(0.1, min_aff, 2, max_iter=max_iter)
     worst = 0.0
-    for lo, hi in ((0, 16), (0, 32), (0, 40)):            # largest frame of the call: 16, 32, 40 detections
+    for lo, hi in ((0, 16), (0, 32), (0, 48)):            # largest frame of the call: 16, 32, 48 detections
         n_persons, kpts = _pack(frames[lo:hi], C, Kj)
-        aff = engine.associate(n_persons, kpts.astype(np.float32), prm)
+        kpts = kpts if f64 else kpts.astype(np.float32)
+        assert as_packed(kpts)[1] == (P2S_F64 if f64 else P2S_F32)
+        aff = engine.associate(n_persons, kpts, prm)
         for f, per_cam in enumerate(frames[lo:hi]):
             N = int(n_persons[f].sum())
             cum = np.cumsum([0] + [len(p) for p in per_cam])
@@ -142,7 +142,23 @@ def test_every_matrix_order(engine, max_iter):
             d = float(np.abs(aff[f, :N, :N] - ref).max())
             worst = max(worst, d)
             assert d <= 1e-9, (hi, N, d)
-    print(f'orders 1..40, max_iter {max_iter}: worst |d| = {worst:.3e}')
+    print(f'orders 1..48, {"float64" if f64 else "float32"}, max_iter {max_iter}: worst |d| = {worst:.3e}')
+
+
+@pytest.mark.parametrize('max_iter', [20, 3])
+def test_every_matrix_order(engine, max_iter):
+    """Frames of 1 .. 48 detections (odd and even orders, empty cameras, one frame per order, up to
+    P2S_MAX_PERSONS_TOTAL): the symmetric one-wave kernel up to 32 -- its 16-row form when the largest frame of a call
+    has at most 16 -- and the general kernel above, against the oracle; converged result and the continuous iterate
+    after 3 passes.  float32 keypoints."""
+    _every_order(engine, max_iter, False)
+
+
+@pytest.mark.parametrize('max_iter', [20, 3])
+def test_every_matrix_order_float64(engine, max_iter):
+    """The same orders through the float64 instantiations (keypoints that are not float32-representable, as a JSON
+    file's numbers usually are not)."""
+    _every_order(engine, max_iter, True)
 
 
 def test_partial_iterations_match_oracle(engine, golden_dir):
@@ -215,20 +231,122 @@ def test_single_person_matches_reference_goldens(engine, golden_dir):
 def test_single_person_matches_oracle_on_random_trials(engine, C, min_cams, thr, seed):
     """More cameras, tighter thresholds (deeper camera-removal levels, more than 64 combinations per
     frame, frames where nothing qualifies) against the pinned oracle."""
+    _random_single_trial(engine, C, min_cams, thr, seed, False)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('C,min_cams,thr,seed', [(3, 2, 8.0, 1), (4, 2, 4.0, 2), (6, 3, 6.0, 3), (8, 4, 5.0, 4), (5, 2, 0.5, 5)])
+def test_single_person_float32_matches_oracle_on_random_trials(engine, C, min_cams, thr, seed):
+    """The same trials with the keypoints rounded to float32: the float32 instantiation of the kernel (the one the
+    product takes for float32-representable JSON numbers), the oracle on the same rounded numbers."""
+    _random_single_trial(engine, C, min_cams, thr, seed, True)
+
+
+def _random_single_trial(engine, C, min_cams, thr, seed, f32):
     from e2e_common import make_single_scene
     from oracle import association_single_ref as sr
+    from pose2sim_amd.engine import P2S_F32, P2S_F64, as_packed
     cams, frames = make_single_scene(24, C, 26, 100 + seed, n_distract=3 if C <= 5 else 1)
+    if f32:
+        frames = [[[np.asarray(p, dtype=np.float32).astype(np.float64) for p in people] for people in per_cam] for per_cam in frames]
     P = synth.projection_matrices(cams)
     eng = engine
     eng.set_calibration(np.array(P))
     n_persons, tracked = _single_inputs(frames, 18)
+    assert as_packed(tracked)[1] == (P2S_F32 if f32 else P2S_F64)
     comb, err, Q = eng.associate_single(n_persons, tracked, thr, 0.3, min_cams)
     want_c, want_e, want_q = [], [], []
     for per_cam in frames:
         e, cb, q = sr.best_persons_and_cameras(per_cam, sr.persons_combinations([len(p) for p in per_cam]), P, 18, thr,
                                                min_cams, 0.3)
         want_c.append(cb); want_e.append(e); want_q.append(q)
-    _check_single(comb, err, Q, np.array(want_c), np.array(want_e), np.array(want_q), f'C{C}')
+    _check_single(comb, err, Q, np.array(want_c), np.array(want_e), np.array(want_q), f'C{C}' + (' f32' if f32 else ''))
+
+
+def _planted_frame(P, counts, true_pos, rng, noise=1.0, bad_cam=None, dup=None):
+    """One frame of the tracked keypoint: camera c holds counts[c] detections, the person of interest at true_pos[c] and
+    distractors 400-800 px away from it (so that a combination below a threshold of a few px is made of the person
+    only).  bad_cam: that camera's detection of the person is 300 px off, so nothing qualifies until it is switched off.
+    dup = (camera, index): a second, identical detection of the person there (an exact tie between two combinations)."""
+    X = np.array([rng.uniform(-0.5, 0.5), rng.uniform(-0.5, 0.5), rng.uniform(0.8, 1.6), 1.0])
+    per_cam = []
+    for c, n in enumerate(counts):
+        h = P[c] @ X
+        uv = h[:2] / h[2] + rng.normal(0, noise, 2)
+        if c == bad_cam:
+            a = rng.uniform(0, 2 * np.pi)
+            uv = uv + 300.0 * np.array([np.cos(a), np.sin(a)])
+        me = np.array([uv[0], uv[1], rng.uniform(0.5, 1.0)])
+        people = []
+        for i in range(n):
+            if i == true_pos[c] or (dup is not None and dup == (c, i)):
+                people.append(me.copy())
+            else:
+                a = rng.uniform(0, 2 * np.pi)
+                people.append(np.array([*(uv + rng.uniform(400, 800) * np.array([np.cos(a), np.sin(a)])), rng.uniform(0.5, 1.0)]))
+        per_cam.append(people)
+    return per_cam
+
+
+def _digits(index, counts):
+    """Mixed-radix digits of a combination index (itertools.product order: the last camera varies fastest)."""
+    out = []
+    for n in reversed(counts):
+        out.append(index % n)
+        index //= n
+    return out[::-1]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('f32', [False, True])
+def test_single_person_planted_frames(engine, f32):
+    """The person of interest planted among far-away distractors, so that the combination the reference's scan stops at
+    is known: the first one below the threshold at index 63, 64, 65, 127, 128 and 6560 (the last of 3^8); nothing below
+    the threshold at level 0 and the first qualifying combination of level 1 past a pass boundary; exact ties between two
+    combinations of one 64-lane pass (min_cameras = C: level 0 only, every combination looked at, the earliest wins);
+    16 detections on a camera (P2S_MAX_PERSONS_PER_CAM); 12 cameras of 2 detections (4 096 combinations).  float32 and
+    float64 numbers, both against the oracle."""
+    from oracle import association_single_ref as sr
+    from pose2sim_amd.engine import P2S_F32, P2S_F64, as_packed
+    rng = np.random.default_rng(61 + f32)
+    c8, c16, c12 = [3] * 8, [16, 3, 2, 16], [2] * 12
+    first_below = [(c8, _digits(i, c8), {}) for i in (63, 64, 65, 127, 128, 6560) for _ in range(2)]
+    level1 = []
+    for first in (64, 100, 200, 2000):                   # camera 0 off: the first qualifying combination has its digit 0
+        pos = _digits(first, c8)
+        pos[0] = int(rng.integers(1, 3))
+        level1.append((c8, pos, dict(bad_cam=0)))
+    level1 += [(c8, _digits(i, c8), dict(bad_cam=7)) for i in (69, 129)]
+    ties = []
+    for counts in ([2, 2, 4, 4], [4, 4, 2, 2], [1, 4, 4, 4]):
+        for _ in range(6):
+            pos = [int(rng.integers(0, n)) for n in counts]
+            c = int(rng.choice([i for i, n in enumerate(counts) if n > 1]))
+            other = int(rng.choice([i for i in range(counts[c]) if i != pos[c]]))
+            ties.append((counts, pos, dict(noise=2.0, dup=(c, other))))
+    groups = [  # (cameras' seed, C, thr, min_cameras, frames)
+        (31, 8, 8.0, 2, first_below + level1),
+        (32, 4, 0.2, 4, ties),
+        (33, 4, 8.0, 2, [(c16, _digits(i, c16), {}) for i in (1535, 1534, 770, 15)]),
+        (34, 12, 8.0, 2, [(c12, _digits(i, c12), {}) for i in (4095, 2049, 63, 64)]),
+    ]
+    for seed, C, thr, min_cams, specs in groups:
+        cams = synth.make_cameras(C, seed=seed)
+        P = [np.asarray(p) for p in synth.projection_matrices(cams)]
+        engine.set_calibration(np.array(P))
+        frames = [_planted_frame(P, counts, pos, rng, **kw) for counts, pos, kw in specs]
+        if f32:
+            frames = [[[np.asarray(p, dtype=np.float32).astype(np.float64) for p in people] for people in per_cam] for per_cam in frames]
+        n_persons, tracked = _single_inputs(frames, 0)
+        assert as_packed(tracked)[1] == (P2S_F32 if f32 else P2S_F64)
+        comb, err, Q = engine.associate_single(n_persons, tracked, thr, 0.3, min_cams)
+        want_c, want_e, want_q = [], [], []
+        for per_cam in frames:
+            e, cb, q = sr.best_persons_and_cameras(per_cam, sr.persons_combinations([len(p) for p in per_cam]), P, 0, thr,
+                                                   min_cams, 0.3)
+            want_c.append(cb); want_e.append(e); want_q.append(q)
+        _check_single(comb, err, Q, np.array(want_c), np.array(want_e), np.array(want_q), f'planted C{C} thr {thr}')
+        assert np.isfinite(err).all()                   # every planted frame has a solution
 
 
 @pytest.mark.gpu

@@ -23,6 +23,16 @@ FAR_M = 100.0
 TOL_E = 2e-6        # px, relative to max(1, err)
 
 
+def oracle_threads(cap=64):
+    """Threads for the C oracle: the CPUs this process may use, at most `cap`, and no more than OMP_NUM_THREADS where
+    that is set (a share of a larger machine)."""
+    n = min(cap, len(os.sched_getaffinity(0)))
+    omp = os.environ.get('OMP_NUM_THREADS', '')
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
+
+
 @pytest.fixture(scope='module', params=['auto', 'worklist', 'onetile', 'twotiles', 'noscreen'])
 def engine(request):
     """auto: the pooled kernel (persistent waves, fp32 screen + fp64 evaluation of the survivors) where it applies, else the
@@ -289,7 +299,7 @@ def test_multi_chunk_calls_equal_the_whole_oracle_run(engine, C, F):
         Qp, ep, np_, mp = engine.triangulate(xyl[lo:hi], prm)
         assert np.array_equal(Qp, Q[lo:hi], equal_nan=True) and np.array_equal(ep, err[lo:hi], equal_nan=True)
         assert np.array_equal(np_, nex[lo:hi]) and np.array_equal(mp, mask[lo:hi])
-    threads = min(64, len(os.sched_getaffinity(0)))
+    threads = oracle_threads()
     Qr, er, nr, mr = tri_oracle.triangulate_batch(xyl.astype(np.float64), wl['P'], None, swap, 0.3, 15.0, 2, threads=threads)
     _compare(Q, err, nex, mask, Qr, er, nr, mr, f'{F * K} units, C={C}')
 
@@ -305,7 +315,7 @@ def test_two_camera_geometry_every_unit_against_the_oracle(engine, C):
     wl = synth.make_config(F, C, K, 1, seed=5 + C)
     engine.set_calibration(wl['P'])
     Q, err, nex, mask = engine.triangulate(wl['xyl'], engine.tri_params(15.0, 0.3, 2))
-    threads = min(64, len(os.sched_getaffinity(0)))
+    threads = oracle_threads()
     Qr, er, nr, mr = tri_oracle.triangulate_batch(wl['xyl'].astype(np.float64), wl['P'], None, swap, 0.3, 15.0, 2, threads=threads)
     dq = _compare(Q, err, nex, mask, Qr, er, nr, mr, f'C={C}')
     assert dq <= 2e-8, dq
@@ -329,7 +339,7 @@ def test_many_cameras_every_unit_against_the_oracle(engine, name, F, C, min_cams
     engine.set_calibration(wl['P'], wl['cams'] if undistort else None)
     prm = engine.tri_params(15.0, 0.3, min_cams, undistort, lr_swap)
     Q, err, nex, mask = engine.triangulate(x64 if f64 else wl['xyl'], prm, swap if lr_swap else None)
-    threads = min(64, len(os.sched_getaffinity(0)))
+    threads = oracle_threads()
     Qr, er, nr, mr = tri_oracle.triangulate_batch(x64, wl['P'], wl['cams'] if undistort else None, swap, 0.3, 15.0, min_cams,
                                                   lr_swap, undistort, threads=threads)
     _compare(Q, err, nex, mask, Qr, er, nr, mr, name)
@@ -350,7 +360,7 @@ def test_cfg4_shape_every_unit_against_the_oracle(engine):
     engine.set_calibration(wl['P'])
     prm = engine.tri_params(15.0, 0.3, 3)
     Q, err, nex, mask = engine.triangulate(wl['xyl'], prm)
-    threads = min(64, len(os.sched_getaffinity(0)))
+    threads = oracle_threads()
     Qr, er, nr, mr = tri_oracle.triangulate_batch(wl['xyl'].astype(np.float64), wl['P'], None, swap, 0.3, 15.0, 3, threads=threads)
     _compare(Q, err, nex, mask, Qr, er, nr, mr, 'C=16 K=131 min_cams=3')
     # odd first block, odd block count: the same numbers through the unaligned store path
@@ -379,7 +389,7 @@ def test_pooled_search_slots_and_tile_pairing(C, p_outlier, F, singles_pct):
         Q, err, nex, mask = eng.triangulate(wl['xyl'], prm)
     finally:
         eng.close()
-    threads = min(64, len(os.sched_getaffinity(0)))
+    threads = oracle_threads()
     Qr, er, nr, mr = tri_oracle.triangulate_batch(wl['xyl'].astype(np.float64), wl['P'], None, list(range(26)), 0.3, 15.0, 2, threads=threads)
     _compare(Q, err, nex, mask, Qr, er, nr, mr, f'C={C} outliers {p_outlier} singles {singles_pct}%')
 
@@ -428,7 +438,7 @@ def test_screen_changes_nothing(name, F, C, K, min_cams, f64, gen, tiles):
     assert evals[1]['screened_subsets'] == evals[0]['screened_subsets'] == evals[0]['subsets_evaluated']
     if evals[0]['subsets_evaluated'] > 1000:
         assert evals[1]['subsets_evaluated'] < 0.5 * evals[0]['subsets_evaluated'], f'{name}: the screen let {evals[1]} of {evals[0]} through'
-    threads = min(64, len(os.sched_getaffinity(0)))
+    threads = oracle_threads()
     Qr, er, nr, mr = tri_oracle.triangulate_batch(wl['xyl'].astype(np.float64), wl['P'], None, list(range(K)), 0.3, 15.0, min_cams, threads=threads)
     _compare(*outs[1], Qr, er, nr, mr, f'{name}, {tiles} tiles')
     print(f'{name}, {tiles} tiles: {evals[1]["subsets_evaluated"]} of {evals[0]["subsets_evaluated"]} subsets evaluated in fp64')
@@ -576,7 +586,7 @@ def test_deep_levels_spread_over_the_gpu(C, min_cams, lr_swap, undistort, f64):
         got = eng.triangulate(x, prm, swap if lr_swap else None)
         for a, b in zip(ref, got):
             assert np.array_equal(a, b, equal_nan=True)
-        threads = min(64, len(os.sched_getaffinity(0)))
+        threads = oracle_threads()
         Qr, er, nr, mr = tri_oracle.triangulate_batch(x64, wl['P'], wl['cams'] if undistort else None, swap, 0.3, 8.0, min_cams,
                                                       lr_swap, undistort, threads=threads)
         _compare(got[0], got[1], got[2], got[3], Qr, er, nr, mr, f'deep C={C}')

@@ -168,8 +168,8 @@ def test_screen_on_equals_screen_off(engines, case):
           f'{stats[1]["subsets_evaluated"]} of {stats[0]["subsets_evaluated"]} subsets evaluated in fp64')
     if lik == 'clamped':
         from oracle import tri_oracle
-        from test_tri_gpu import _compare
-        threads = min(16, len(os.sched_getaffinity(0)))
+        from test_tri_gpu import _compare, oracle_threads
+        threads = oracle_threads(16)
         Qr, er, nr, mr = tri_oracle.triangulate_batch(wl['xyl'].astype(np.float64), wl['P'], None, list(range(K)), lik_thr, thr,
                                                       min_cams, threads=threads)
         _compare(*on, Qr, er, nr, mr, _case_id(case))
