@@ -187,8 +187,11 @@ int p2s_butterworth_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const d
  *   P2S_FILTER_KALMAN    kalman_filter_1d :316-434: constant-acceleration Kalman filter (predict, Joseph-form update per
  *                        sample) and, with smooth != 0, the Rauch-Tung-Striebel smoother over every run of >= 4 samples
  *                        that are neither NaN nor 0; params = {1 / frame_rate, measurement_noise, process_noise, smooth}.
- *                        PARITY UNPINNED: the reference takes both from filterpy (not importable where this was built);
- *                        restated from filterpy's published algorithm
+ *                        The initial state of a run is {z0, z1 - z0, z2 - 2 z1 + z0}: the reference's differences are not
+ *                        divided by the frame period (:342-351).  The caller decides what smooth means (the reference:
+ *                        only int(smooth) == 1).  The reference takes both passes from filterpy (not importable where
+ *                        this was built); restated from filterpy's published algorithm and checked against goldens
+ *                        recorded through the reference's set-up code and against an exact multiprecision solve
  * All pointers are HOST pointers; the call blocks. */
 #define P2S_FILTER_HAMPEL 1
 #define P2S_FILTER_GAUSSIAN 2

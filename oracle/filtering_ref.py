@@ -10,9 +10,11 @@ there, they are present on the GPU box and pinned by the goldens recorded from t
 * butterworth_on_speed_filter_1d  Pose2Sim/filtering.py:474-510
 * gaussian_filter_1d      Pose2Sim/filtering.py:513-529
 * median_filter_1d        Pose2Sim/filtering.py:561-577
-* kalman_filter_1d        Pose2Sim/filtering.py:316-434 -- PARITY UNPINNED: the reference calls filterpy (KalmanFilter.batch_filter,
-                          rts_smoother, Q_discrete_white_noise; version not pinned in pyproject.toml), which is not importable
-                          here; its published algorithm is restated and no golden vector exists
+* kalman_filter_1d        Pose2Sim/filtering.py:316-434 -- the reference calls filterpy (KalmanFilter.batch_filter, rts_smoother,
+                          Q_discrete_white_noise), which is not importable here and has never run here; its published
+                          algorithm is restated.  Pinned by tests/golden/kalman_units.npz: the reference's own set-up code
+                          (state, F, H, P, R, Q, the `smooth` test, run splitting) executed with a stand-in for filterpy's
+                          recursion, and that stand-in checked against an exact multiprecision solve (tests/kalman_exact.py)
 * compute_bone_lengths / compute_smoothness / compute_missing_data / compute_symmetry
                           Pose2Sim/Utilities/trc_evaluate.py:114-280
 """
@@ -124,9 +126,12 @@ def median_filter_1d(col, kernel_size):
 
 
 def kalman_filter_1d(col, frame_rate, trust_ratio, smooth=True):
-    """filtering.py:316-434 with filterpy's published algorithms restated (PARITY UNPINNED, see the header): constant-
-    acceleration model of one coordinate (state position / velocity / acceleration), measurement noise 20, process noise
-    20 * trust_ratio, predict + update per sample (KalmanFilter.batch_filter), then the Rauch-Tung-Striebel smoother."""
+    """filtering.py:316-434 with filterpy's published algorithms restated (pinned by kalman_units.npz, see the header):
+    constant-acceleration model of one coordinate (state position / velocity / acceleration), measurement noise 20,
+    process noise 20 * trust_ratio, predict + update per sample (KalmanFilter.batch_filter), then the Rauch-Tung-Striebel
+    smoother -- only when int(smooth) == 1: the reference tests `smooth == True` on int(smooth) (:395, :418), so 2 does
+    not smooth.  The initial state is [z0, z1 - z0, z2 - 2 z1 + z0]: the reference differentiates with derivate_array's
+    default dt = 1 (:342-351), the differences are NOT divided by the frame period."""
     measurement_noise = 20
     process_noise = measurement_noise * int(trust_ratio)
     out = np.array(col, dtype=np.float64)
@@ -140,7 +145,7 @@ def kalman_filter_1d(col, frame_rate, trust_ratio, smooth=True):
         if len(seq) < 4:                                                                   # :428
             continue
         z = out[seq]
-        x = np.array([z[0], np.diff(z, 1)[0] / dt, np.diff(np.diff(z) / dt)[0] / dt])       # :343-351
+        x = np.array([z[0], np.diff(z)[0], np.diff(np.diff(z))[0]])                         # :342-351 (dt = 1 there)
         P = np.eye(3) * measurement_noise                                                   # :377
         xs, Ps = [], []
         I = np.eye(3)
@@ -155,7 +160,7 @@ def kalman_filter_1d(col, frame_rate, trust_ratio, smooth=True):
             P = IKH @ P @ IKH.T + K @ R @ K.T
             xs.append(x.copy()); Ps.append(P.copy())
         xs, Ps = np.array(xs), np.array(Ps)
-        if smooth:                                                                          # rts_smoother
+        if int(smooth) == 1:                                                                # :395 rts_smoother
             for k in range(len(z) - 2, -1, -1):
                 Pp = F @ Ps[k] @ F.T + Q
                 Kk = Ps[k] @ F.T @ np.linalg.inv(Pp)

@@ -211,9 +211,12 @@ __global__ void __launch_bounds__(64) p2s_one_euro_kernel(const P2sColFilterArgs
 // kalman_filter_1d (filtering.py:316-434): constant-acceleration Kalman filter of one coordinate (state position, velocity,
 // acceleration; the measurement is the position) over every run of >= 4 samples that are neither NaN nor 0, then the
 // Rauch-Tung-Striebel smoother.  The reference builds it from filterpy (KalmanFilter.batch_filter: predict, then update in
-// Joseph form, per sample; rts_smoother) -- filterpy is not importable here, so this follows its published algorithm and
-// is PARITY UNPINNED (checked against oracle/filtering_ref.py only).  One lane per column; the forward pass leaves its
-// means and covariances (12 doubles per sample) in `work` for the smoother.
+// Joseph form, per sample; rts_smoother) -- filterpy is not importable here, so this follows its published algorithm.  It
+// is checked against goldens recorded through the reference's own set-up code with a stand-in for filterpy's recursion,
+// and against an exact multiprecision solve of the model (tests/golden/kalman_units.npz).  The initial state is
+// [z0, z1 - z0, z2 - 2 z1 + z0]: the reference differentiates with dt = 1 (:342-351), the differences are NOT divided by
+// the frame period.  One lane per column; the forward pass leaves its means and covariances (12 doubles per sample) in
+// `work` for the smoother.
 struct M3 { double m[9]; };
 __device__ __forceinline__ M3 mul3(const M3 &A, const M3 &B) {
     M3 C;
@@ -270,9 +273,10 @@ __global__ void __launch_bounds__(64) p2s_kalman_kernel(const P2sColFilterArgs a
             f = r;
             continue;
         }
-        // initial state from the first three samples (:343-351), covariance I * measurement_noise (:377)
+        // initial state: first and second difference of the first three samples, undivided (:342-351, derivate_array's
+        // default dt = 1); covariance I * measurement_noise (:376)
         const double z0 = in[f * S], z1 = in[(f + 1) * S], z2 = in[(f + 2) * S];
-        double x0 = z0, x1 = (z1 - z0) / dt, x2 = ((z2 - z1) / dt - (z1 - z0) / dt) / dt;
+        double x0 = z0, x1 = z1 - z0, x2 = (z2 - z1) - (z1 - z0);
         M3 P{{meas, 0.0, 0.0, 0.0, meas, 0.0, 0.0, 0.0, meas}};
         for (int64_t i = f; i < r; ++i) {
             // predict: x = F x, P = F P F^T + Q

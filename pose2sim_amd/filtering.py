@@ -15,9 +15,11 @@ What runs where:
   cross-validation (scipy.interpolate.make_smoothing_spline's criterion and minimize_scalar's bounded search, one lane
   per run); the median / MAD normalisation of 'auto' is computed by the host
 
-* ``kalman`` (:316-434) .................................................... p2s_kalman_kernel -- PARITY UNPINNED: the
-  reference takes the filter and the smoother from filterpy, which is not importable where this was built; the kernel
-  follows filterpy's published algorithm and is checked against oracle/filtering_ref.py only
+* ``kalman`` (:316-434) .................................................... p2s_kalman_kernel.  The reference takes the
+  filter and the smoother from filterpy, which is not importable where this was built and has never run here; the kernel
+  follows filterpy's published algorithm.  It is pinned by goldens for which the reference's own set-up code (state, F, H,
+  P, R, Q, the ``smooth`` test, run splitting) was executed with a stand-in for filterpy's recursion, the stand-in being
+  checked against an exact multiprecision solve of the same model (tests/golden/make_golden_kalman.py)
 
 Coefficients and kernel weights come from the very SciPy calls the reference makes, so the kernels reproduce its numbers
 to rounding.  ``loess`` needs statsmodels, which is not importable where this was built: it is refused with
@@ -99,12 +101,14 @@ def one_euro_filter(data, frame_rate, min_cutoff=2.5, beta=0.9, d_cutoff=1.0, en
 def kalman_filter(data, frame_rate, trust_ratio, smooth=True, engine=None):
     """kalman_filter_1d (filtering.py:402-434) on every column: constant-acceleration Kalman filter (measurement noise 20,
     process noise 20 * trust_ratio) and Rauch-Tung-Striebel smoother over every run of >= 4 samples that are neither NaN
-    nor 0.  PARITY UNPINNED: the reference takes both from filterpy, which is not importable here -- the kernel follows
-    filterpy's published algorithm and is checked against oracle/filtering_ref.py only."""
+    nor 0.  The smoother runs only when int(smooth) == 1: the reference tests `smooth == True` on int(smooth) (:395,
+    :418), so 2 filters without smoothing.  The reference takes both passes from filterpy, which has never run here; the
+    kernel follows filterpy's published algorithm and is checked against goldens recorded through the reference's own
+    set-up code and against an exact multiprecision solve."""
     engine = engine or _make_engine()
     measurement_noise = 20
     return engine.filter_columns(FILTER_KALMAN, data, [1.0 / frame_rate, float(measurement_noise), float(measurement_noise * int(trust_ratio)),
-                                                       1.0 if int(smooth) else 0.0])
+                                                       1.0 if int(smooth) == 1 else 0.0])
 
 
 def gcv_spline_filter(data, cutoff, smoothing_factor, frame_rate, engine=None):

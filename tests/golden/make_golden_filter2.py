@@ -5,7 +5,8 @@
 * filter_all (:728-830) with reject_outliers = true (the shipped Demo_SinglePerson configuration: Hampel, then
   Butterworth order 4 at 6 Hz) and with each of the other types, on a written .trc file: the text it produces.
 
-Kalman, GCV spline and LOESS are not recorded: they need filterpy / statsmodels, which are not importable here.
+Kalman is recorded by make_golden_kalman.py (through a stand-in for filterpy's recursion), the GCV spline by
+make_golden_gcv.py; LOESS is not recorded: it needs statsmodels, which is not importable here.
 """
 import os
 import sys

@@ -1,6 +1,6 @@
 """Randomised sweep of the column filters: random lengths (1 .. 600 frames), column counts, gap patterns and parameters,
 every column of every case against oracle/filtering_ref.py (the reference's own SciPy / NumPy calls; Kalman: the
-restatement, parity unpinned).     python tests/sweeps/fuzz_filters.py [n_cases] [seed]"""
+restatement, pinned by tests/test_kalman_host.py).     python tests/sweeps/fuzz_filters.py [n_cases] [seed]"""
 import os, sys, warnings
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np

@@ -259,11 +259,100 @@ def test_filter_all_with_outlier_rejection_on_the_gpu(engine, gold2):
         shutil.rmtree(root, ignore_errors=True)
 
 
+@pytest.fixture(scope='module')
+def gold_kalman(golden_dir):
+    return np.load(os.path.join(golden_dir, 'kalman_units.npz'))
+
+
+def _distance(got, want, what):
+    assert got.shape == want.shape and np.array_equal(np.isnan(got), np.isnan(want)), f'{what}: NaN pattern'
+    ok = ~np.isnan(want)
+    return float((np.abs(got[ok] - want[ok]) / np.maximum(1.0, np.abs(want[ok]))).max()) if ok.any() else 0.0
+
+
+def test_kalman_kernel_against_the_golden_columns(engine, gold_kalman):
+    """p2s_kalman_kernel against every column of kalman_units.npz: what the reference's own kalman_filter_1d returned
+    (filterpy's recursion replaced by the stand-in, see tests/test_kalman_host.py) and the exact posterior means of the
+    same model, both within TOL; samples outside the runs of >= 4 bit-identical to the input.  Measured on an MI355X: worst
+    3.2e-15 from the reference's outputs, 2.2e-15 from the exact values."""
+    import test_kalman_host as host
+    from pose2sim_amd import filtering
+    g = gold_kalman
+    worst_ref = worst_exact = 0.0
+    for i in range(int(g['n_cols'])):
+        col, rate, trust, smooth = host._case(g, i)
+        got = filtering.kalman_filter(col.reshape(-1, 1), rate, trust, smooth, engine)[:, 0]
+        what = f'column {i} ({rate} fps, trust {trust}, smooth {smooth!r})'
+        d_ref, d_exact = _distance(got, g[f'col{i}_out'], what), _distance(got, g[f'col{i}_exact'], what)
+        print(f'{what}: |kernel - reference| = {d_ref:.2e}, |kernel - exact| = {d_exact:.2e}')
+        assert d_ref <= TOL and d_exact <= TOL, f'{what}: {d_ref:.3e} from the reference, {d_exact:.3e} from the exact values'
+        worst_ref, worst_exact = max(worst_ref, d_ref), max(worst_exact, d_exact)
+        filtered = np.zeros(len(col), dtype=bool)
+        for seq in host._runs(col):
+            filtered[seq] = True
+        assert np.array_equal(got[~filtered], col[~filtered], equal_nan=True), what
+    print(f'worst: {worst_ref:.2e} from the reference, {worst_exact:.2e} from the exact values')
+
+
+def test_kalman_kernel_all_golden_columns_in_one_launch(engine, gold_kalman):
+    """The same columns side by side in one matrix per (frame rate, trust, smooth) group, padded with NaN to a common
+    length: neighbours in a wave must not disturb each other."""
+    import test_kalman_host as host
+    from pose2sim_amd import filtering
+    g = gold_kalman
+    groups = {}
+    for i in range(int(g['n_cols'])):
+        col, rate, trust, smooth = host._case(g, i)
+        groups.setdefault((rate, trust, repr(smooth)), []).append(i)
+    for (rate, trust, smooth), members in groups.items():
+        L = max(len(g[f'col{i}_in']) for i in members)
+        data = np.full((L, len(members)), np.nan)
+        for k, i in enumerate(members):
+            data[:len(g[f'col{i}_in']), k] = g[f'col{i}_in']
+        got = filtering.kalman_filter(data, rate, trust, host.SMOOTH_VALUES[smooth], engine)
+        for k, i in enumerate(members):
+            n = len(g[f'col{i}_in'])
+            _close(got[:n, k], g[f'col{i}_out'], f'column {i} in a group of {len(members)}')
+            assert np.isnan(got[n:, k]).all()
+
+
+def test_initial_state_of_the_kalman_kernel(engine, gold_kalman):
+    """The first filtered sample of a filter-only run at 25 and 240 fps against the closed form for the reference's
+    initial state [z0, z1 - z0, z2 - 2 z1 + z0] (tests/test_kalman_host.check_initial_state)."""
+    import test_kalman_host as host
+    from pose2sim_amd import filtering
+    for i, z, rate, trust in host.initial_state_cases(gold_kalman):
+        got = filtering.kalman_filter(z.reshape(-1, 1), rate, trust, False, engine)[:, 0]
+        host.check_initial_state(got[0], z, rate, trust, f'kernel, column {i} ({rate} fps, trust {trust})')
+
+
+def test_filter_all_kalman_on_the_gpu(engine, gold_kalman):
+    """filter_all with type = 'kalman' (smoother, and the filter alone) against the text the reference wrote: header
+    lines and frame / time columns exactly, coordinates within TOL."""
+    import shutil
+    import tempfile
+    from pathlib import Path
+    import test_kalman_host as host
+    from pose2sim_amd import filtering
+    g = gold_kalman
+    root = tempfile.mkdtemp(prefix='p2s_kal_')
+    try:
+        for i in range(int(g['n_files'])):
+            trial, cfg = host._write_trial(Path(root), g, i)
+            paths = filtering.filter_all(cfg, engine=engine)
+            assert [os.path.basename(p) for p in paths] == [str(g[f'file{i}_out_name'])]
+            d = host.compare_trc_text(open(paths[0]).read(), str(g[f'file{i}_out_text']), f'file {i}', TOL)
+            print(f'file {i}: worst coordinate {d:.2e} from the recorded text')
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+
+
 def test_kalman_kernel_against_the_restatement(engine):
-    """p2s_kalman_kernel against oracle/filtering_ref.kalman_filter_1d -- PARITY UNPINNED: the reference takes the filter
-    and the smoother from filterpy, which is not importable here, so no golden exists; both sides follow filterpy's
-    published algorithm (predict, Joseph-form update, rts_smoother).  Runs of every length around the 4-sample limit,
-    NaN and zero gaps, a column that is all NaN, filter and smoother, two trust ratios; 1e-9 relative."""
+    """p2s_kalman_kernel against oracle/filtering_ref.kalman_filter_1d, which tests/test_kalman_host.py pins to the
+    reference's recorded outputs and to the exact posterior means.  Runs of every length around the 4-sample limit, NaN
+    and zero gaps, a column that is all NaN, filter and smoother, two trust ratios, 30 / 60 / 240 fps, every column; then
+    a .trc-sized matrix (20 000 frames x 156 columns, the [frame][col][12] work buffer over three blocks of 64 lanes) of
+    which a sample of columns goes through the oracle's Python loop; 1e-9 relative."""
     from oracle import filtering_ref as fr
     from pose2sim_amd import filtering
     rng = np.random.default_rng(33)
@@ -274,15 +363,32 @@ def test_kalman_kernel_against_the_restatement(engine):
     data[rng.random((F, ncol)) < 0.004] = 0.0
     data[:, 5] = np.nan
     data[10:13, 6] = np.nan; data[16, 6] = np.nan; data[21, 6] = 0.0           # runs of 3, 4 and more
-    for trust, smooth in ((500, True), (500, False), (20, True)):
-        got = filtering.kalman_filter(data, 60, trust, smooth, engine)
-        for c in range(0, ncol, 3):
-            _close(got[:, c], fr.kalman_filter_1d(data[:, c], 60, trust, smooth), f'kalman trust {trust} smooth {smooth} column {c}')
-        assert np.array_equal(got[:, 5], data[:, 5], equal_nan=True)
+    for rate, trust, smooth, frames in ((60, 500, True, F), (60, 500, False, F), (60, 20, True, F),
+                                        (30, 500, True, 1_000), (240, 20, False, 1_000), (240, 500, True, 1_000)):
+        got = filtering.kalman_filter(data[:frames], rate, trust, smooth, engine)
+        for c in range(ncol):
+            _close(got[:, c], fr.kalman_filter_1d(data[:frames, c], rate, trust, smooth), f'kalman {rate} fps trust {trust} smooth {smooth} column {c}')
+        assert np.array_equal(got[:, 5], data[:frames, 5], equal_nan=True)
     for F2 in (1, 3, 4, 5):
         small = rng.normal(1, 0.1, (F2, 9))
         want = np.stack([fr.kalman_filter_1d(small[:, c], 30, 500, True) for c in range(9)], 1)
         _close(filtering.kalman_filter(small, 30, 500, True, engine), want, f'kalman F={F2}')
+    # the size the other filters are tested at, with the gap pattern of test_matrix_against_the_oracle
+    rng = np.random.default_rng(12)
+    F, ncol = 20_000, 156
+    t = np.arange(F)[:, None] / 60.0
+    data = 1.0 + 0.5 * np.sin(2 * np.pi * (0.5 + rng.random(ncol)) * t) + rng.normal(0, 0.01, (F, ncol))
+    data[rng.random((F, ncol)) < 0.002] = np.nan
+    data[rng.random((F, ncol)) < 0.001] = 0.0
+    for c in range(0, ncol, 7):
+        g = int(rng.integers(0, F - 400)); data[g:g + int(rng.integers(1, 400)), c] = np.nan
+    data[:, 3] = np.nan
+    data[:50, 5] = 0.0
+    for trust, smooth, cols in ((500, True, (0, 3, 5, 7, 63, 64, 100, 127, 128, 155)), (20, False, (0, 5, 63, 64, 155))):
+        got = filtering.kalman_filter(data, 60, trust, smooth, engine)
+        for c in cols:
+            _close(got[:, c], fr.kalman_filter_1d(data[:, c], 60, trust, smooth), f'kalman at .trc size, trust {trust} smooth {smooth} column {c}')
+        assert np.array_equal(np.isnan(got), np.isnan(data)) and np.array_equal(got == 0.0, data == 0.0)
 
 
 def test_random_filter_cases():

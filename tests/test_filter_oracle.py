@@ -203,8 +203,9 @@ def test_trc_evaluate_matches_the_reference(tmp_path, gold):
 
 
 def test_kalman_stage_runs_and_reports(work_dir, gold, caplog):
-    """type = 'kalman' (PARITY UNPINNED: filterpy is not importable): the stage runs, names its file
-    and prints the reference's line for it (filtering.py:703); the numbers are the oracle restatement's here."""
+    """type = 'kalman': the stage runs, names its file and prints the reference's line for it (filtering.py:703); the
+    numbers are the oracle's, column by column, which tests/test_kalman_host.py pins to the reference's recorded outputs
+    and to the exact posterior means (filter_all against the text the reference wrote is checked there too)."""
     import logging
     from pose2sim_amd import filtering
     trial, cfg = _write_trial(work_dir, gold, 0)
@@ -218,11 +219,22 @@ def test_kalman_stage_runs_and_reports(work_dir, gold, caplog):
     from pose2sim_amd import trc
     frames, times, data, markers, header = trc.load_trc(paths[0])
     assert np.isfinite(data).any()
+    raw = trc.load_trc(str(trial / 'pose-3d' / str(gold['file0_name'])))[2]
+    rate = int(gold['file0_prm'][2])
+    assert data.shape == raw.shape and np.array_equal(np.isnan(data), np.isnan(raw))
+    changed = 0
+    for c in range(raw.shape[1]):
+        want = fr.kalman_filter_1d(raw[:, c], rate, 500, True)
+        ok = ~np.isnan(want)
+        if ok.any():
+            assert (np.abs(data[ok, c] - want[ok]) / np.maximum(1.0, np.abs(want[ok]))).max() <= 1e-9, c
+            changed += int((want[ok] != raw[ok, c]).sum())
+    assert changed > raw.size // 2                       # it did filter
 
 
 def test_kalman_oracle_tracks_a_smooth_signal():
-    """Sanity of the restatement itself (it is all that pins the kernel): a noisy parabola comes back closer to the truth
-    with the smoother than with the filter alone, runs shorter than 4 samples and gaps are left alone."""
+    """Sanity of the restatement itself: a noisy parabola comes back closer to the truth with the smoother than with the
+    filter alone, from the first frame of every run on; runs shorter than 4 samples and gaps are left alone."""
     rng = np.random.default_rng(2)
     t = np.arange(400) / 60.0
     truth = 1.0 + 0.8 * t - 0.3 * t * t
@@ -232,7 +244,7 @@ def test_kalman_oracle_tracks_a_smooth_signal():
     col[106] = 0.0
     filt = fr.kalman_filter_1d(col, 60, 500, smooth=False)
     smo = fr.kalman_filter_1d(col, 60, 500, smooth=True)
-    ok = np.r_[5:100, 110:395]
+    ok = np.r_[0:100, 110:395]
     assert np.abs(smo[ok] - truth[ok]).mean() < np.abs(col[ok] - truth[ok]).mean()
     assert np.abs(smo[ok] - truth[ok]).mean() <= np.abs(filt[ok] - truth[ok]).mean() * 1.05
     assert np.isnan(smo[100:103]).all() and np.array_equal(smo[103:106], [0.5, 0.6, 0.7]) and smo[106] == 0.0
