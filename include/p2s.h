@@ -228,6 +228,42 @@ int p2s_gcv_spline_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const do
 int p2s_trc_metrics_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_markers, const double *xyz, int32_t n_bones,
                          const int32_t *bones, double *bone_len, double *bone_stats, double *accel, int64_t *missing);
 
+/* ---- a .trc back onto the image planes (Utilities/reproj_from_trc_calib.py:446-475) ------------------------------------
+ * One projection per (frame, marker, camera), float64 throughout: replaces the frame x keypoint x camera loop around
+ * reprojection() (:183-201) / cv2.projectPoints (:455), the rounding to one decimal (:461-462) and the out-of-image mask
+ * (:469-475).
+ *   Q      [n_frames][n_markers][3]  the markers in the Z-up frame (X, Y, Z): a .trc row holds (Y, Z, X) per marker and
+ *                                    the caller undoes that order; NaN = missing
+ *   flags  0: pinhole.  P [n_cams][n_frames_p][12] with n_frames_p = 1 (static cameras) or n_frames (one matrix per
+ *             frame: moving and / or zooming cameras); x = P0.q / P2.q, y = P1.q / P2.q, q = (X, Y, Z, 1).  Kmat, dist,
+ *             Rmat and T are not read.
+ *          P2S_REPROJ_DISTORTED: cv2.projectPoints with Kmat [n_cams][9], dist [n_cams][5] (k1, k2, p1, p2, k3), Rmat
+ *             [n_cams][9], T [n_cams][3]: z == 0 -> 1, the skew term ignored; the same device code as the triangulation
+ *             kernels' reprojection.  Static cameras only (n_frames_p = 1); P is not read.
+ *   sizes  [n_cams][2] image width, height
+ * outputs, [n_cams][n_frames][n_markers][2] (x, y) each:
+ *   uv_raw the pixels as computed (may be NULL)
+ *   uv     what the reference stores: np.round(v, decimals=1) = rint(10 v) / 10 with ties to even, then x and y both NaN
+ *          unless 0 <= x < width and 0 <= y < height on the ROUNDED values; a NaN or infinite projection comes out NaN.
+ * All of Q and of the outputs is device-resident during the call: n_frames x n_markers x n_cams x 32 bytes (16 without
+ * uv_raw) must fit, or the call fails with P2S_ERR_OOM.  HOST pointers; blocks. */
+#define P2S_REPROJ_DISTORTED 1
+int p2s_reproject_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_markers, const double *Q, int32_t n_cams, int64_t n_frames_p,
+                       const double *P, const double *Kmat, const double *dist, const double *Rmat, const double *T,
+                       const double *sizes, int32_t flags, double *uv_raw, double *uv);
+/* Milliseconds the kernel of this context's last p2s_reproject_host took (HIP events around it; 0 for an empty call). */
+int p2s_reproject_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
+/* dataset_to_openpose (Utilities/reproj_from_trc_calib.py:245-286) for every camera and frame at once, on at most 16 host
+ * threads (no GPU involved): file `<dir c>/<name_root>_cam<c+1, 2 digits>_openpose_<f, 4 digits>.json` holds json.dumps of
+ * the reference's dictionary -- version 1.3, one person with "person_id": [-1], in "pose_keypoints_2d" per output position
+ * k the triplet x, y, 1 of marker marker_index[k] (floats as Python's repr) or 0.0, 0.0, 0 when either is NaN, then the
+ * seven empty lists.  uv [n_cams][n_frames][n_markers][2] as p2s_reproject_host returns it; marker_index [n_out];
+ * directory names back to back as in p2s_json_parse, and they must exist.  n_written (may be NULL): files completed.  On
+ * a failure the other files are still written and the first failing path (in camera, frame order) is reported. */
+int p2s_write_openpose_files(const char *dir_paths, const int64_t *dir_offsets, const char *name_root, int32_t n_cams,
+                             int64_t n_frames, int32_t n_markers, int32_t n_out, const int32_t *marker_index,
+                             const double *uv, int32_t n_threads, int64_t *n_written);
+
 /* ---- synchronization (synchronize_cams_all, synchronization.py:1346-1612) ------------------------------------------
  * Speeds: replaces the per-camera pandas / scipy work of :1562-1584 (interpolate_zeros_nans :1565, bfill().ffill(),
  * signal.filtfilt :1568, vert_speed :1271-1288, abs().sum(axis=1) :1579, filtfilt of the sum :1585).  coords: the cameras'

@@ -69,6 +69,8 @@ struct p2s_ctx {
     int n_cams = 0;
     bool full_calib = false;     // K, dist, R, T, newK were provided
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev_rp[2] = {nullptr, nullptr};        // around the kernel of p2s_reproject_host
+    float reproj_kernel_ms = -1.0f;                  // p2s_reproject_kernel_ms: the last call's kernel time
     hipStream_t side_stream = nullptr;               // search kernels run here, beside the next chunk's streaming pass
     hipEvent_t ev_k1[2] = {nullptr, nullptr}, ev_k2[2] = {nullptr, nullptr};
     Scratch in, swap, q, err, nexcl, mask, aux0, aux1;
@@ -219,6 +221,8 @@ int p2s_create(int device_id, p2s_ctx **out) {
     HIP_TRY(hipMemset(c->d_assoc_stats, 0, sizeof(unsigned long long) * P2S_STAT_SHARDS * P2S_STAT_STRIDE));
     HIP_TRY(hipEventCreate(&c->ev0));
     HIP_TRY(hipEventCreate(&c->ev1));
+    HIP_TRY(hipEventCreate(&c->ev_rp[0]));
+    HIP_TRY(hipEventCreate(&c->ev_rp[1]));
     HIP_TRY(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
     for (int i = 0; i < 2; ++i) {
         HIP_TRY(hipEventCreateWithFlags(&c->ev_k1[i], hipEventDisableTiming));
@@ -244,6 +248,8 @@ int p2s_destroy(p2s_ctx *ctx) {
     if (ctx->d_sub_off) (void)hipFree(ctx->d_sub_off);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
+    for (int i = 0; i < 2; ++i)
+        if (ctx->ev_rp[i]) (void)hipEventDestroy(ctx->ev_rp[i]);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     if (ctx->side_stream) { (void)hipStreamSynchronize(ctx->side_stream); (void)hipStreamDestroy(ctx->side_stream); }
     for (int i = 0; i < 2; ++i) {
@@ -1138,6 +1144,83 @@ int p2s_trc_metrics_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_markers, cons
         HIP_TRY(hipMemcpyAsync(missing, m.missing, (size_t)n_markers * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return P2S_OK;
+}
+
+int p2s_reproject_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_markers, const double *Q, int32_t n_cams, int64_t n_frames_p,
+                       const double *P, const double *Kmat, const double *dist, const double *Rmat, const double *T,
+                       const double *sizes, int32_t flags, double *uv_raw, double *uv) {
+    if (!ctx) return fail(P2S_ERR_INVALID_ARG, "null context");
+    if (n_frames < 0 || n_markers < 0) return fail(P2S_ERR_INVALID_ARG, "bad shape: %lld frames, %d markers", (long long)n_frames, n_markers);
+    if (n_cams < 1 || n_cams > P2S_MAX_CAMS) return fail(P2S_ERR_INVALID_ARG, "n_cams=%d outside [1, %d]", n_cams, P2S_MAX_CAMS);
+    if (flags & ~P2S_REPROJ_DISTORTED) return fail(P2S_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
+    const bool distorted = (flags & P2S_REPROJ_DISTORTED) != 0;
+    if (distorted) {
+        if (n_frames_p != 1)
+            return fail(P2S_ERR_INVALID_ARG, "distorted projection takes static cameras: n_frames_p=%lld, expected 1", (long long)n_frames_p);
+        if (!Kmat || !dist || !Rmat || !T) return fail(P2S_ERR_INVALID_ARG, "distorted projection needs K, dist, R and T");
+    } else {
+        if (n_frames_p != 1 && n_frames_p != n_frames)
+            return fail(P2S_ERR_INVALID_ARG, "n_frames_p=%lld is neither 1 nor n_frames=%lld", (long long)n_frames_p, (long long)n_frames);
+        if (!P) return fail(P2S_ERR_INVALID_ARG, "null P");
+    }
+    if (!sizes) return fail(P2S_ERR_INVALID_ARG, "null sizes");
+    if (!uv) return fail(P2S_ERR_INVALID_ARG, "null uv");
+    const int64_t n_units = n_frames * (int64_t)n_markers;
+    ctx->reproj_kernel_ms = 0.0f;
+    if (n_units == 0) return P2S_OK;
+    if (!Q) return fail(P2S_ERR_INVALID_ARG, "null Q");
+    if (n_units > ((int64_t)1 << 38) / n_cams) return fail(P2S_ERR_INVALID_ARG, "%lld units x %d cameras is too large", (long long)n_units, n_cams);
+    const size_t q_b = (size_t)n_units * 3 * sizeof(double);
+    const size_t out_b = (size_t)n_units * n_cams * 2 * sizeof(double);
+    const size_t cam_b = distorted ? sizeof(P2sCam) * (size_t)n_cams : (size_t)n_cams * n_frames_p * 12 * sizeof(double);
+    int rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = ctx->in.ensure(q_b)) != P2S_OK) return rc;
+    if ((rc = ctx->aux0.ensure(cam_b)) != P2S_OK) return rc;
+    if ((rc = ctx->aux1.ensure((size_t)n_cams * 2 * sizeof(double))) != P2S_OK) return rc;
+    if ((rc = ctx->q.ensure(out_b)) != P2S_OK) return rc;
+    if (uv_raw && (rc = ctx->swap.ensure(out_b)) != P2S_OK) return rc;
+    P2sReprojArgs a{};
+    a.Q = (const double *)ctx->in.p;
+    a.sizes = (const double *)ctx->aux1.p;
+    a.uv = (double *)ctx->q.p;
+    a.uv_raw = uv_raw ? (double *)ctx->swap.p : nullptr;
+    a.n_units = n_units; a.Fp = n_frames_p; a.K = n_markers; a.C = n_cams;
+    std::vector<P2sCam> cams;
+    if (distorted) {
+        cams.resize((size_t)n_cams);
+        std::memset(cams.data(), 0, sizeof(P2sCam) * (size_t)n_cams);
+        for (int c = 0; c < n_cams; ++c) {
+            P2sCam &cam = cams[(size_t)c];
+            const double *K = Kmat + 9 * c;
+            cam.fx = K[0]; cam.fy = K[4]; cam.cx = K[2]; cam.cy = K[5];     // the skew term is ignored, as in cv2.projectPoints
+            std::memcpy(cam.k, dist + 5 * c, sizeof cam.k);
+            std::memcpy(cam.R, Rmat + 9 * c, sizeof cam.R);
+            std::memcpy(cam.T, T + 3 * c, sizeof cam.T);
+        }
+        a.cams = (const P2sCam *)ctx->aux0.p;
+        HIP_TRY(hipMemcpyAsync(ctx->aux0.p, cams.data(), cam_b, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        a.P = (const double *)ctx->aux0.p;
+        HIP_TRY(hipMemcpyAsync(ctx->aux0.p, P, cam_b, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->aux1.p, sizes, (size_t)n_cams * 2 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->in.p, Q, q_b, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_rp[0], ctx->stream));
+    HIP_TRY(p2s_launch_reproject(a, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_rp[1], ctx->stream));
+    HIP_TRY(hipMemcpyAsync(uv, a.uv, out_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (uv_raw) HIP_TRY(hipMemcpyAsync(uv_raw, a.uv_raw, out_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));          // `cams` is pageable host memory: alive until here
+    HIP_TRY(hipEventElapsedTime(&ctx->reproj_kernel_ms, ctx->ev_rp[0], ctx->ev_rp[1]));
+    return P2S_OK;
+}
+
+int p2s_reproject_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) {
+    if (!ctx || !elapsed_ms) return fail(P2S_ERR_INVALID_ARG, "null argument");
+    if (ctx->reproj_kernel_ms < 0.0f) return fail(P2S_ERR_INVALID_ARG, "p2s_reproject_host has not run on this context");
+    *elapsed_ms = ctx->reproj_kernel_ms;
     return P2S_OK;
 }
 

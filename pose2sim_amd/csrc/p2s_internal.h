@@ -253,4 +253,18 @@ struct P2sMetricsArgs {
 };
 hipError_t p2s_launch_trc_metrics(const P2sMetricsArgs &a, hipStream_t s);
 
+// p2s_reproj.hip: 3D markers onto the image planes (Utilities/reproj_from_trc_calib.py:446-475)
+struct P2sReprojArgs {
+    const double *Q;             // [n_frames][K][3], Z-up (X, Y, Z); NaN = missing
+    const double *P;             // plain mode: [C][Fp][12]
+    const P2sCam *cams;          // distorted mode: [C] (R, T, fx, fy, cx, cy, k read); NULL = plain mode
+    const double *sizes;         // [C][2] width, height
+    double *uv_raw;              // [C][n_frames][K][2] unrounded pixels, or NULL
+    double *uv;                  // [C][n_frames][K][2] rounded to one decimal, NaN outside the image
+    int64_t n_units;             // n_frames * K
+    int64_t Fp;                  // 1, or n_frames: one projection matrix per frame
+    int32_t K, C;
+};
+hipError_t p2s_launch_reproject(const P2sReprojArgs &a, hipStream_t s);
+
 #endif

@@ -3,11 +3,13 @@
 // `frame \t time \t v1 \t v2 ...`, floats as Python's repr() prints them (shortest digits that round-trip, fixed
 // notation for 1e-4 <= |v| < 1e16, otherwise d.ddde+XX), NaN as an empty field.  pandas formats every value
 // through a Python object; at 100 k frames x 78 columns that is ~20 s, this writer takes a fraction of a second.
+#include <cerrno>
 #include <charconv>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <thread>
 #include <vector>
 #include <atomic>
@@ -153,6 +155,111 @@ int p2s_trc_append_rows(const char *path, int64_t n_rows, int32_t n_cols, const 
     }
     if (fclose(fh) != 0 && rc == P2S_OK) rc = p2s_set_error(P2S_ERR_INVALID_ARG, "error closing %s", path);
     return rc;
+}
+
+int p2s_write_openpose_files(const char *dir_paths, const int64_t *dir_offsets, const char *name_root, int32_t n_cams,
+                             int64_t n_frames, int32_t n_markers, int32_t n_out, const int32_t *marker_index,
+                             const double *uv, int32_t n_threads, int64_t *n_written) {
+    if (n_written) *n_written = 0;
+    if (n_cams < 0 || n_frames < 0 || n_markers < 0 || n_out < 0 || !name_root || (n_cams > 0 && (!dir_paths || !dir_offsets)) ||
+        (n_out > 0 && !marker_index) || (n_cams > 0 && n_frames > 0 && n_out > 0 && !uv))
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "bad arguments");
+    for (int32_t i = 0; i < n_out; ++i)
+        if (marker_index[i] < 0 || marker_index[i] >= n_markers)
+            return p2s_set_error(P2S_ERR_INVALID_ARG, "output position %d names marker %d of %d", i, marker_index[i], n_markers);
+    const int64_t n_files = (int64_t)n_cams * n_frames;
+    if (n_files == 0) return P2S_OK;
+    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
+    if (nt < 1) nt = 1;
+    if (nt > 16) nt = 16;                                     // file writing: never more than 16 host threads
+    const int64_t grain = 64;
+    if ((int64_t)nt > (n_files + grain - 1) / grain) nt = (int)((n_files + grain - 1) / grain);
+    static const char head[] = "{\"version\": 1.3, \"people\": [{\"person_id\": [-1], \"pose_keypoints_2d\": [";
+    static const char tail[] = "], \"face_keypoints_2d\": [], \"hand_left_keypoints_2d\": [], \"hand_right_keypoints_2d\": [], "
+                               "\"pose_keypoints_3d\": [], \"face_keypoints_3d\": [], \"hand_left_keypoints_3d\": [], "
+                               "\"hand_right_keypoints_3d\": []}]}";
+    std::atomic<int64_t> next{0}, done{0}, first_bad{n_files};
+    std::vector<int> errs((size_t)nt, 0);
+    std::vector<std::string> bad_path((size_t)nt);
+    std::vector<int64_t> bad_file((size_t)nt, n_files);
+    auto work_files = [&](int t) {
+        std::vector<char> buf(sizeof head + sizeof tail + (size_t)n_out * 64);
+        std::string path;
+        char num[32];
+        while (true) {
+            const int64_t b = next.fetch_add(grain);
+            if (b >= n_files) break;
+            const int64_t e = b + grain < n_files ? b + grain : n_files;
+            for (int64_t i = b; i < e; ++i) {
+                const int64_t c = i / n_frames, f = i % n_frames;
+                char *o = buf.data();
+                memcpy(o, head, sizeof head - 1);
+                o += sizeof head - 1;
+                const double *row = uv + (c * n_frames + f) * (int64_t)n_markers * 2;
+                for (int32_t k = 0; k < n_out; ++k) {
+                    const double x = row[2 * marker_index[k]], y = row[2 * marker_index[k] + 1];
+                    if (k) { *o++ = ','; *o++ = ' '; }
+                    if (x != x || y != y) {
+                        memcpy(o, "0.0, 0.0, 0", 11);
+                        o += 11;
+                    } else {
+                        o = py_repr(o, x);
+                        *o++ = ','; *o++ = ' ';
+                        o = py_repr(o, y);
+                        memcpy(o, ", 1", 3);
+                        o += 3;
+                    }
+                }
+                memcpy(o, tail, sizeof tail - 1);
+                o += sizeof tail - 1;
+                path.assign(dir_paths + dir_offsets[c], (size_t)(dir_offsets[c + 1] - dir_offsets[c]));
+                path += '/';
+                path += name_root;
+                snprintf(num, sizeof num, "_cam%02d_openpose_%04lld.json", (int)(c + 1), (long long)f);
+                path += num;
+                FILE *fh = fopen(path.c_str(), "wb");
+                const size_t n = (size_t)(o - buf.data());
+                bool ok = fh != nullptr;
+                int err = ok ? 0 : errno;
+                if (ok && fwrite(buf.data(), 1, n, fh) != n) { ok = false; err = errno; }
+                if (fh && fclose(fh) != 0 && ok) { ok = false; err = errno; }
+                if (ok) {
+                    done.fetch_add(1);
+                } else if (i < bad_file[(size_t)t]) {
+                    bad_file[(size_t)t] = i; errs[(size_t)t] = err; bad_path[(size_t)t] = path;
+                    int64_t cur = first_bad.load();
+                    while (i < cur && !first_bad.compare_exchange_weak(cur, i)) {}
+                }
+            }
+        }
+    };
+    std::atomic<bool> oom{false};
+    auto work = [&](int t) {
+        try {
+            work_files(t);
+        } catch (const std::bad_alloc &) {                    // on a pool thread: reported after the join, never thrown across it
+            oom.store(true);
+        }
+    };
+    try {
+        if (nt <= 1) {
+            work(0);
+        } else {
+            std::vector<std::thread> pool;
+            for (int t = 0; t < nt; ++t) pool.emplace_back(work, t);
+            for (auto &th : pool) th.join();
+        }
+    } catch (const std::bad_alloc &) {
+        return p2s_set_error(P2S_ERR_OOM, "out of host memory while formatting");
+    }
+    if (n_written) *n_written = done.load();
+    if (oom.load()) return p2s_set_error(P2S_ERR_OOM, "out of host memory while formatting");
+    const int64_t bad = first_bad.load();
+    if (bad < n_files)
+        for (int t = 0; t < nt; ++t)
+            if (bad_file[(size_t)t] == bad)
+                return p2s_set_error(P2S_ERR_INVALID_ARG, "cannot write %s: %s", bad_path[(size_t)t].c_str(), strerror(errs[(size_t)t]));
+    return P2S_OK;
 }
 
 }  // extern "C"

@@ -36,6 +36,30 @@ def as_packed(xyl):
     return x64, P2S_F64
 
 
+def write_openpose_files(cam_dirs, name_root, uv, marker_index=None, n_threads=0):
+    """dataset_to_openpose (Utilities/reproj_from_trc_calib.py:245-286) for every camera and frame: the files
+    `<cam_dirs[c]>/<name_root>_cam<c+1>_openpose_<frame>.json` from uv [C][F][K][2], written by the native writer on at
+    most 16 host threads (no GPU involved).  marker_index: the marker of every output position (default: all, in order).
+    -> number of files written."""
+    import os
+    lib = _lib.load()
+    if not hasattr(lib, 'p2s_write_openpose_files'):
+        raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_write_openpose_files: rebuild it')
+    uv = np.ascontiguousarray(uv, dtype=np.float64)
+    if uv.ndim != 4 or uv.shape[3] != 2 or uv.shape[0] != len(cam_dirs):
+        raise P2sError(f'uv has shape {uv.shape}; expected [{len(cam_dirs)}][F][K][2]')
+    Cn, F, K = uv.shape[:3]
+    idx = np.arange(K, dtype=np.int32) if marker_index is None else np.ascontiguousarray(marker_index, dtype=np.int32).reshape(-1)
+    names = [os.fsencode(d) for d in cam_dirs]
+    offsets = np.zeros(Cn + 1, dtype=np.int64)
+    np.cumsum([len(n) for n in names], out=offsets[1:])
+    done = C.c_int64(0)
+    _lib.check(lib.p2s_write_openpose_files(b''.join(names), _ptr(offsets), os.fsencode(name_root), Cn, F, K, len(idx),
+                                            _ptr(idx) if idx.size else None, _ptr(uv) if uv.size else None, int(n_threads),
+                                            C.byref(done)))
+    return done.value
+
+
 class Engine:
     def __init__(self, device=0):
         self._lib = _lib.load()
@@ -264,6 +288,66 @@ class Engine:
         p = lambda x: _ptr(x) if x.size else None                           # noqa: E731
         _lib.check(self._lib.p2s_trc_metrics_host(self._h, F, K, p(xyz), nb, p(bones), p(bone_len), p(bone_stats), p(accel), p(missing)))
         return bone_len, bone_stats, accel, missing
+
+    # -- a .trc back onto the image planes (Utilities/reproj_from_trc_calib.py:446-475) --------------------------------
+    def reproject(self, Q, P=None, cal=None, sizes=None, raw=False):
+        """Q [F][K][3] (Z-up X, Y, Z; NaN = missing) onto C cameras.  Either P [C][Fp][3][4] (or [C][3][4]) with Fp = 1
+        or F -- the pinhole projection, one matrix per frame for moving / zooming cameras -- or cal, a dict with 'K',
+        'dist' (k1, k2, p1, p2[, k3]), 'R_mat' and 'T' per camera: cv2.projectPoints with distortion, static cameras.
+        sizes [C][2] (width, height).  -> uv [C][F][K][2] rounded to one decimal with NaN outside the image, as the
+        reference stores it; with raw=True (uv, uv_raw), uv_raw being the pixels as computed."""
+        if not hasattr(self._lib, 'p2s_reproject_host'):
+            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_reproject_host: rebuild it')
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        if Q.ndim != 3 or Q.shape[2] != 3:
+            raise P2sError(f'Q has shape {Q.shape}; expected [F][K][3]')
+        if (P is None) == (cal is None):
+            raise P2sError('give either P (pinhole) or cal (distorted), not both')
+        F, K = Q.shape[:2]
+        args = [None] * 5
+        if cal is None:
+            P = np.asarray(P, dtype=np.float64)
+            if P.ndim == 3:
+                P = P[:, None]
+            if P.ndim != 4 or P.shape[2:] != (3, 4):
+                raise P2sError(f'P has shape {P.shape}; expected [C][Fp][3][4]')
+            P = np.ascontiguousarray(P)
+            Cn, Fp = P.shape[:2]
+            args[0] = _ptr(P)
+            flags = 0
+        else:
+            Cn, Fp = len(cal['K']), 1
+            Km = np.ascontiguousarray(np.asarray(cal['K'], dtype=np.float64).reshape(Cn, 9))
+            d = np.zeros((Cn, 5))
+            for c in range(Cn):
+                dc = np.asarray(cal['dist'][c], dtype=np.float64).ravel()
+                if len(dc) > 5 and np.any(dc[5:] != 0):
+                    raise P2sError('only k1,k2,p1,p2[,k3] distortion terms are supported')
+                d[c, :min(5, len(dc))] = dc[:5]
+            R = np.ascontiguousarray(np.asarray(cal['R_mat'], dtype=np.float64).reshape(Cn, 9))
+            T = np.ascontiguousarray(np.asarray(cal['T'], dtype=np.float64).reshape(Cn, 3))
+            keep = (Km, d, R, T)
+            args[1:] = [_ptr(x) for x in keep]
+            flags = _lib.P2S_REPROJ_DISTORTED
+        sizes = np.ascontiguousarray(sizes, dtype=np.float64)
+        if sizes.shape != (Cn, 2):
+            raise P2sError(f'sizes has shape {sizes.shape}; expected [{Cn}][2]')
+        uv = np.empty((Cn, F, K, 2))
+        uv_raw = np.empty((Cn, F, K, 2)) if raw else None
+        _lib.check(self._lib.p2s_reproject_host(self._h, F, K, _ptr(Q) if Q.size else None, Cn, Fp, *args, _ptr(sizes), flags,
+                                                _ptr(uv_raw) if raw else None, _ptr(uv)))
+        return (uv, uv_raw) if raw else uv
+
+    def reproject_kernel_ms(self):
+        """Kernel time of the last reproject() call, from HIP events around it."""
+        if not hasattr(self._lib, 'p2s_reproject_kernel_ms'):
+            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_reproject_kernel_ms: rebuild it')
+        ms = C.c_float(0)
+        _lib.check(self._lib.p2s_reproject_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def write_openpose_files(self, cam_dirs, name_root, uv, marker_index=None, n_threads=0):
+        return write_openpose_files(cam_dirs, name_root, uv, marker_index, n_threads)
 
     # -- synchronization (synchronization.py:1271-1343, 1541-1585) -------------------------------------------------------
     def sync_speeds(self, coords, b, a, zi):
