@@ -264,6 +264,43 @@ int p2s_write_openpose_files(const char *dir_paths, const int64_t *dir_offsets, 
                              int64_t n_frames, int32_t n_markers, int32_t n_out, const int32_t *marker_index,
                              const double *uv, int32_t n_threads, int64_t *n_written);
 
+/* ---- exact order statistics of columns ---------------------------------------------------------------------------------
+ * For each of n_cols contiguous float64 columns of n_rows entries (data is column-major: column c starts at
+ * data + c * n_rows), NaN entries skipped: counts[c] = the number m of non-NaN entries, out[c][j] = the entry at 0-based
+ * position ranks[j] of the sorted non-NaN entries; a negative rank counts from the top (-1 = the largest); a rank outside
+ * [0, m) gives NaN, so an all-NaN column gives NaN throughout.  Exact: a radix select on the bit patterns, no
+ * arithmetic.  -0.0 orders before +0.0.  np.nanmedian is np.mean of out at (m - 1) / 2 and at m / 2 (of one entry when m is odd).  n_rows < 2^31;
+ * counts may be NULL.  HOST pointers; blocks. */
+int p2s_column_order_stats_host(p2s_ctx *ctx, int64_t n_rows, int32_t n_cols, const double *data, int32_t n_ranks,
+                                const int64_t *ranks, double *out, int64_t *counts);
+
+/* ---- 2D keypoint jitter (Utilities/keypoint_jitter_analyze.py:143-325) --------------------------------------------------
+ * compute_displacements, compute_bb_areas, detect_jitter, np.argwhere and classify_pattern for every camera at once,
+ * float64 throughout and bit for bit the reference's numbers.  series: the cameras' [n_frames[c]][26][3] (x, y,
+ * confidence) tables back to back; n_frames[c] >= 1 and < 2^31.  With rows[c] = n_frames[c] - 1, every output holds the
+ * cameras back to back and any of them may be NULL:
+ *   displacements  per camera [26][rows[c]] -- COLUMN-major, one keypoint's series contiguous: sqrt(dx*dx + dy*dy)
+ *                  between consecutive frames, NaN unless both confidences are > 0.1
+ *   areas          per camera [n_frames[c]]: (xmax - xmin) * (ymax - ymin) over the keypoints with confidence > 0.1 when
+ *                  there are at least 2 (a NaN coordinate among them gives NaN), otherwise NaN
+ *   medians, thresholds [n_cams][26]: np.nanmedian of every displacement column; median * multiplier, 10 where the
+ *                  median is 0;  median_area [n_cams]: np.nanmedian of the areas
+ *   mask           per camera [rows[c]][26] bytes: displacement > threshold
+ *   counts         [n_cams][26]: events per keypoint
+ *   events         [event_capacity][4] int32 (camera, frame = row + 1, keypoint, pattern): the set cells of the mask in
+ *                  camera, row, keypoint order (np.argwhere per camera).  pattern at frame row + 1, the first that holds:
+ *                  0 'A' at least 2 valid keypoints and xmin < 10, ymin < 10, xmax > width - 10 or ymax > height - 10;
+ *                  1 'C' area and median area not NaN and area < 0.5 * median area; 2 'D' confidence < 0.3; 3 'E'.
+ *   n_events       the number of events, whatever the capacity: when it exceeds event_capacity only the first
+ *                  event_capacity were written and the caller asks again with room for all.
+ * HOST pointers; blocks. */
+int p2s_jitter_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, const double *series, double multiplier,
+                    double image_width, double image_height, double *displacements, double *areas, double *medians,
+                    double *thresholds, double *median_area, uint8_t *mask, int32_t *counts, int64_t event_capacity,
+                    int32_t *events, int64_t *n_events);
+/* Milliseconds the kernels of this context's last p2s_jitter_host took (HIP events around them). */
+int p2s_jitter_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
+
 /* ---- synchronization (synchronize_cams_all, synchronization.py:1346-1612) ------------------------------------------
  * Speeds: replaces the per-camera pandas / scipy work of :1562-1584 (interpolate_zeros_nans :1565, bfill().ffill(),
  * signal.filtfilt :1568, vert_speed :1271-1288, abs().sum(axis=1) :1579, filtfilt of the sum :1585).  coords: the cameras'
@@ -417,6 +454,30 @@ int p2s_json_gather_largest_person(const p2s_json_batch *batch, const int32_t *k
  * P2S_ERR_INVALID_ARG with the first failure's path and errno text in p2s_last_error(). */
 int p2s_copy_files(const char *src_paths, const int64_t *src_offsets, const char *dst_paths, const int64_t *dst_offsets,
                    int64_t n_files, int32_t n_threads, int8_t *ok);
+/* load_keypoints_series / _select_person (Utilities/keypoint_jitter_analyze.py:50-140) over one camera's batch, the
+ * files in the order given; sequential, since every choice depends on the one before.  out [n_files][n_kpts][3] float64:
+ * the chosen person's first 3 * n_kpts numbers, NaN for a file without one.  A person is a candidate when its list has
+ * at least 3 * n_kpts numbers and a keypoint with confidence > conf_threshold and a non-NaN x.  One candidate: taken.
+ * Several, after an earlier choice: the one with the strictly smallest mean 2D distance to that choice over the
+ * keypoints valid in both (the first on ties; no shared keypoint, or a NaN mean: not eligible) -- the mean is summed in
+ * np.mean's order.  Otherwise the candidate with the most confidences > conf_threshold, the first on ties.
+ * status [n_files], detail [n_files] (may be NULL):
+ *   P2S_TRACK_SELECTED      detail = the person's index in "people"
+ *   P2S_TRACK_NO_PEOPLE     an object without "people", or with an empty or null one
+ *   P2S_TRACK_NO_CANDIDATE  persons, none of them a candidate
+ *   P2S_TRACK_LONG_LIST     a person's list is longer than 3 * n_kpts (the reference's reshape raises); detail = its length
+ *   P2S_TRACK_BAD_FILE      unreadable, or not JSON
+ *   P2S_TRACK_BAD_CONTENT   the top level is not an object, "people" is neither a list nor null, a person is not an
+ *                           object, or a list holds something that is not a number (null included)
+ * The negative ones end the reference's run; the rows after them are still filled as if the file held no people. */
+#define P2S_TRACK_SELECTED 1
+#define P2S_TRACK_NO_PEOPLE 0
+#define P2S_TRACK_NO_CANDIDATE 2
+#define P2S_TRACK_LONG_LIST (-1)
+#define P2S_TRACK_BAD_FILE (-2)
+#define P2S_TRACK_BAD_CONTENT (-3)
+int p2s_json_select_tracked_person(const p2s_json_batch *batch, int32_t n_kpts, double conf_threshold, double *out,
+                                   int32_t *status, int32_t *detail);
 
 /* ---- .trc data rows (host threads) ---------------------------------------------------------------------------
  * Replaces DataFrame.to_csv in make_trc (triangulation.py:214): appends n_rows lines

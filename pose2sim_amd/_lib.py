@@ -20,6 +20,8 @@ P2S_ERR_GCV_SHORT_RUN, P2S_ERR_GCV_ILL_POSED, P2S_ERR_GCV_NO_MINIMUM, P2S_ERR_GC
 P2S_JSON_PERSON_NO_LIST, P2S_JSON_PERSON_NOT_NUMERIC = -1, -2
 P2S_ERR_SYNC_PADLEN = -10
 P2S_REPROJ_DISTORTED = 1
+P2S_TRACK_SELECTED, P2S_TRACK_NO_PEOPLE, P2S_TRACK_NO_CANDIDATE = 1, 0, 2
+P2S_TRACK_LONG_LIST, P2S_TRACK_BAD_FILE, P2S_TRACK_BAD_CONTENT = -1, -2, -3
 
 
 class TriParams(C.Structure):
@@ -86,6 +88,11 @@ SIGNATURES = {
     'p2s_reproject_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     'p2s_write_openpose_files': (C.c_int, [C.c_char_p, C.c_void_p, C.c_char_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
                                            C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
+    'p2s_column_order_stats_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'p2s_jitter_host': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double]
+                        + [C.c_void_p] * 7 + [C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
+    'p2s_jitter_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    'p2s_json_select_tracked_person': (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     'p2s_timing_begin': (C.c_int, [C.c_void_p]),
     'p2s_timing_end': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     'p2s_json_parse': (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]),
@@ -111,7 +118,8 @@ SIGNATURES = {
 
 # entry points a library built before them lacks (P2S_LIB may name one): left unbound, and the feature is refused
 OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_host', 'p2s_json_gather_largest_person',
-            'p2s_copy_files', 'p2s_reproject_host', 'p2s_reproject_kernel_ms', 'p2s_write_openpose_files'}
+            'p2s_copy_files', 'p2s_reproject_host', 'p2s_reproject_kernel_ms', 'p2s_write_openpose_files',
+            'p2s_column_order_stats_host', 'p2s_jitter_host', 'p2s_jitter_kernel_ms', 'p2s_json_select_tracked_person'}
 
 _lib = None
 

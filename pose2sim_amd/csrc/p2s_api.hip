@@ -71,6 +71,8 @@ struct p2s_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_rp[2] = {nullptr, nullptr};        // around the kernel of p2s_reproject_host
     float reproj_kernel_ms = -1.0f;                  // p2s_reproject_kernel_ms: the last call's kernel time
+    hipEvent_t ev_jt[2] = {nullptr, nullptr};        // around the kernels of p2s_jitter_host
+    float jitter_kernel_ms = -1.0f;                  // p2s_jitter_kernel_ms
     hipStream_t side_stream = nullptr;               // search kernels run here, beside the next chunk's streaming pass
     hipEvent_t ev_k1[2] = {nullptr, nullptr}, ev_k2[2] = {nullptr, nullptr};
     Scratch in, swap, q, err, nexcl, mask, aux0, aux1;
@@ -223,6 +225,8 @@ int p2s_create(int device_id, p2s_ctx **out) {
     HIP_TRY(hipEventCreate(&c->ev1));
     HIP_TRY(hipEventCreate(&c->ev_rp[0]));
     HIP_TRY(hipEventCreate(&c->ev_rp[1]));
+    HIP_TRY(hipEventCreate(&c->ev_jt[0]));
+    HIP_TRY(hipEventCreate(&c->ev_jt[1]));
     HIP_TRY(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
     for (int i = 0; i < 2; ++i) {
         HIP_TRY(hipEventCreateWithFlags(&c->ev_k1[i], hipEventDisableTiming));
@@ -250,6 +254,8 @@ int p2s_destroy(p2s_ctx *ctx) {
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (int i = 0; i < 2; ++i)
         if (ctx->ev_rp[i]) (void)hipEventDestroy(ctx->ev_rp[i]);
+    for (int i = 0; i < 2; ++i)
+        if (ctx->ev_jt[i]) (void)hipEventDestroy(ctx->ev_jt[i]);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     if (ctx->side_stream) { (void)hipStreamSynchronize(ctx->side_stream); (void)hipStreamDestroy(ctx->side_stream); }
     for (int i = 0; i < 2; ++i) {
@@ -1221,6 +1227,144 @@ int p2s_reproject_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) {
     if (!ctx || !elapsed_ms) return fail(P2S_ERR_INVALID_ARG, "null argument");
     if (ctx->reproj_kernel_ms < 0.0f) return fail(P2S_ERR_INVALID_ARG, "p2s_reproject_host has not run on this context");
     *elapsed_ms = ctx->reproj_kernel_ms;
+    return P2S_OK;
+}
+
+int p2s_column_order_stats_host(p2s_ctx *ctx, int64_t n_rows, int32_t n_cols, const double *data, int32_t n_ranks,
+                                const int64_t *ranks, double *out, int64_t *counts) {
+    if (!ctx) return fail(P2S_ERR_INVALID_ARG, "null context");
+    if (n_rows < 0 || n_rows >= ((int64_t)1 << 31) || n_cols < 0 || n_ranks < 0)
+        return fail(P2S_ERR_INVALID_ARG, "bad shape: %lld rows, %d columns, %d ranks", (long long)n_rows, n_cols, n_ranks);
+    if (n_cols == 0) return P2S_OK;
+    if ((n_rows > 0 && !data) || (n_ranks > 0 && (!ranks || !out))) return fail(P2S_ERR_INVALID_ARG, "null argument");
+    const size_t data_b = (size_t)n_rows * n_cols * sizeof(double);
+    const size_t rank_b = (size_t)n_ranks * sizeof(int64_t), out_b = (size_t)n_cols * n_ranks * sizeof(double);
+    const size_t cnt_b = (size_t)n_cols * sizeof(int64_t);
+    int rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = ctx->in.ensure(data_b ? data_b : 8)) != P2S_OK) return rc;
+    if ((rc = ctx->aux0.ensure(rank_b + 8)) != P2S_OK) return rc;
+    if ((rc = ctx->aux1.ensure(out_b + cnt_b + 8)) != P2S_OK) return rc;
+    P2sOrderArgs a{};
+    a.data = (const double *)ctx->in.p;
+    a.ranks = (const int64_t *)ctx->aux0.p;
+    a.counts = (int64_t *)ctx->aux1.p;                            // the 8-byte counts first: both parts stay aligned
+    a.out = (double *)((char *)ctx->aux1.p + cnt_b);
+    a.n_rows = n_rows; a.n_cols = n_cols; a.n_ranks = n_ranks;
+    if (data_b) HIP_TRY(hipMemcpyAsync(ctx->in.p, data, data_b, hipMemcpyHostToDevice, ctx->stream));
+    if (rank_b) HIP_TRY(hipMemcpyAsync(ctx->aux0.p, ranks, rank_b, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(p2s_launch_order_stats(a, ctx->stream));
+    if (out_b) HIP_TRY(hipMemcpyAsync(out, a.out, out_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, a.counts, cnt_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return P2S_OK;
+}
+
+int p2s_jitter_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, const double *series, double multiplier,
+                    double image_width, double image_height, double *displacements, double *areas, double *medians,
+                    double *thresholds, double *median_area, uint8_t *mask, int32_t *counts, int64_t event_capacity,
+                    int32_t *events, int64_t *n_events) {
+    if (!ctx) return fail(P2S_ERR_INVALID_ARG, "null context");
+    if (n_cams < 1 || n_cams > 65535) return fail(P2S_ERR_INVALID_ARG, "n_cams=%d outside [1, 65535]", n_cams);
+    if (!n_frames || !series) return fail(P2S_ERR_INVALID_ARG, "null argument");
+    if (event_capacity < 0 || (event_capacity > 0 && !events)) return fail(P2S_ERR_INVALID_ARG, "event_capacity=%lld without room", (long long)event_capacity);
+    constexpr int K = P2S_JITTER_KPTS, NS = K + 1;
+    const size_t C = (size_t)n_cams;
+    // host tables: frame_off [C+1], tile_base [C+1], col_off [C*27], col_len [C*27]
+    std::vector<int64_t> tab(2 * (C + 1) + 2 * C * NS);
+    int64_t *frame_off = tab.data(), *tile_base = frame_off + C + 1, *col_off = tile_base + C + 1, *col_len = col_off + C * NS;
+    int64_t max_frames = 0;
+    frame_off[0] = tile_base[0] = 0;
+    for (size_t c = 0; c < C; ++c) {
+        if (n_frames[c] < 1 || n_frames[c] >= ((int64_t)1 << 31))
+            return fail(P2S_ERR_INVALID_ARG, "camera %zu has %lld frames; expected 1 .. 2^31 - 1", c, (long long)n_frames[c]);
+        frame_off[c + 1] = frame_off[c] + n_frames[c];
+        tile_base[c + 1] = tile_base[c] + (n_frames[c] - 1 + 255) / 256;
+        max_frames = std::max(max_frames, n_frames[c]);
+    }
+    const int64_t frames = frame_off[C], rows = frames - n_cams, n_tiles = tile_base[C];
+    if (frames > ((int64_t)1 << 33)) return fail(P2S_ERR_INVALID_ARG, "%lld frames are too many", (long long)frames);
+    for (size_t c = 0; c < C; ++c) {                              // displacement columns, then the areas, in one allocation
+        const int64_t R = n_frames[c] - 1;
+        for (int k = 0; k < K; ++k) { col_off[c * NS + k] = K * (frame_off[c] - (int64_t)c) + k * R; col_len[c * NS + k] = R; }
+        col_off[c * NS + K] = K * rows + frame_off[c];
+        col_len[c * NS + K] = n_frames[c];
+    }
+    const size_t series_b = (size_t)frames * K * 3 * sizeof(double), disp_b = (size_t)rows * K * sizeof(double);
+    const size_t area_b = (size_t)frames * sizeof(double), tab_b = tab.size() * sizeof(int64_t);
+    // small device block after the tables: stats [C*27][2] f64, stat counts [C*27] i64, medians, thresholds [C*26] f64,
+    // median area [C] f64, n_events i64, counts [C*26] i32
+    const size_t o_stats = tab_b, o_scnt = o_stats + C * NS * 16, o_med = o_scnt + C * NS * 8, o_thr = o_med + C * K * 8;
+    const size_t o_marea = o_thr + C * K * 8, o_nev = o_marea + C * 8, o_cnt = o_nev + 8, small_b = o_cnt + C * K * 4;
+    int rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = ctx->in.ensure(series_b)) != P2S_OK) return rc;
+    if ((rc = ctx->q.ensure(disp_b + area_b)) != P2S_OK) return rc;
+    if ((rc = ctx->aux0.ensure(small_b)) != P2S_OK) return rc;
+    if ((rc = ctx->aux1.ensure((size_t)n_tiles * 16 + 16)) != P2S_OK) return rc;
+    if ((rc = ctx->mask.ensure((size_t)rows * K + 16)) != P2S_OK) return rc;
+    if ((rc = ctx->nexcl.ensure((size_t)frames)) != P2S_OK) return rc;
+    if ((rc = ctx->swap.ensure((size_t)event_capacity * 16 + 16)) != P2S_OK) return rc;
+    char *sm = (char *)ctx->aux0.p;
+    P2sJitterArgs a{};
+    a.series = (const double *)ctx->in.p;
+    a.frame_off = (const int64_t *)sm;
+    a.tile_base = a.frame_off + C + 1;
+    a.disp = (double *)ctx->q.p;
+    a.area = a.disp + (size_t)rows * K;
+    a.edge = (uint8_t *)ctx->nexcl.p;
+    a.stats = (const double *)(sm + o_stats);
+    a.stat_counts = (const int64_t *)(sm + o_scnt);
+    a.medians = (double *)(sm + o_med);
+    a.thresholds = (double *)(sm + o_thr);
+    a.med_area = (double *)(sm + o_marea);
+    a.n_events = (long long *)(sm + o_nev);
+    a.counts = (int32_t *)(sm + o_cnt);
+    a.mask = (uint8_t *)ctx->mask.p;
+    a.tile_off = (long long *)ctx->aux1.p;
+    a.tile_count = (uint32_t *)((char *)ctx->aux1.p + (size_t)n_tiles * 8 + 8);
+    a.events = (int32_t *)ctx->swap.p;
+    a.event_capacity = event_capacity;
+    a.n_tiles = n_tiles; a.max_frames = max_frames;
+    a.multiplier = multiplier; a.x_edge = image_width - 10.0; a.y_edge = image_height - 10.0;
+    a.C = n_cams;
+    P2sOrderArgs o{};
+    o.data = a.disp;
+    o.col_off = a.tile_base + C + 1;
+    o.col_len = o.col_off + C * NS;
+    o.out = (double *)(sm + o_stats);
+    o.counts = (int64_t *)(sm + o_scnt);
+    o.n_cols = n_cams * NS; o.n_ranks = 2;                        // ranks NULL: the two middle positions
+    HIP_TRY(hipMemcpyAsync(sm, tab.data(), tab_b, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(a.counts, 0, C * K * 4, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->in.p, series, series_b, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_jt[0], ctx->stream));
+    HIP_TRY(p2s_launch_jitter(a, o, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_jt[1], ctx->stream));
+    long long found = 0;
+    HIP_TRY(hipMemcpyAsync(&found, a.n_events, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (displacements && disp_b) HIP_TRY(hipMemcpyAsync(displacements, a.disp, disp_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (areas) HIP_TRY(hipMemcpyAsync(areas, a.area, area_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (medians) HIP_TRY(hipMemcpyAsync(medians, a.medians, C * K * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (thresholds) HIP_TRY(hipMemcpyAsync(thresholds, a.thresholds, C * K * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (median_area) HIP_TRY(hipMemcpyAsync(median_area, a.med_area, C * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (mask && rows) HIP_TRY(hipMemcpyAsync(mask, a.mask, (size_t)rows * K, hipMemcpyDeviceToHost, ctx->stream));
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, a.counts, C * K * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                   // `tab` and `found` are host memory: alive until here
+    HIP_TRY(hipEventElapsedTime(&ctx->jitter_kernel_ms, ctx->ev_jt[0], ctx->ev_jt[1]));
+    const int64_t n_copy = std::min<int64_t>(found, event_capacity);
+    if (n_copy > 0) {
+        HIP_TRY(hipMemcpyAsync(events, a.events, (size_t)n_copy * 16, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    if (n_events) *n_events = found;
+    return P2S_OK;
+}
+
+int p2s_jitter_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) {
+    if (!ctx || !elapsed_ms) return fail(P2S_ERR_INVALID_ARG, "null argument");
+    if (ctx->jitter_kernel_ms < 0.0f) return fail(P2S_ERR_INVALID_ARG, "p2s_jitter_host has not run on this context");
+    *elapsed_ms = ctx->jitter_kernel_ms;
     return P2S_OK;
 }
 

@@ -41,16 +41,21 @@ enum PersonStatus : int8_t {
                           // synchronization gather: indexing that value raises in the reference)
 };
 
+enum : int8_t { kPersonNotObject = 1, kPersonHasNull = 2 };                    // Person::flags
+enum : int8_t { kFileTopObject = 1, kFilePeopleNull = 2, kFilePeopleOther = 4 };  // FileRec::flags
+
 struct Person {
     int64_t off;
     int32_t len;
     int8_t status;
+    int8_t flags;         // what the status does not tell apart (p2s_json_select_tracked_person)
 };
 
 struct FileRec {
     int32_t count;        // >= 0: len(people); P2S_JSON_UNREADABLE; P2S_JSON_NO_PEOPLE_LIST
     int32_t thread;
     int64_t first_person; // index into the thread's person vector
+    int8_t flags;         // kFile*: why a valid document has no "people" list
 };
 
 struct Arena {
@@ -67,6 +72,7 @@ struct Parser {
     bool have_people = false;
     size_t people_first = 0;
     int32_t people_count = 0;
+    int8_t file_flags = 0;
 
     inline void ws() {
         while (p < end && (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r')) ++p;
@@ -261,6 +267,7 @@ struct Parser {
         std::vector<double> &v = arena->values;
         person.off = (int64_t)v.size();
         person.status = kPersonOk;
+        person.flags &= (int8_t)~kPersonHasNull;
         ws();
         if (p < end && *p == ']') {
             ++p;
@@ -288,6 +295,7 @@ struct Parser {
             } else if (c == 'n') {
                 if (!literal("null")) return false;
                 d = nan;                                   // numpy: float(None) -> nan
+                person.flags |= kPersonHasNull;
             } else if (c == 't') {
                 if (!literal("true")) return false;
                 d = 1.0;
@@ -316,10 +324,11 @@ struct Parser {
     }
     // One element of the "people" array.
     bool person(std::string &key) {
-        Person rec{0, 0, kPersonNoList};
+        Person rec{0, 0, kPersonNoList, 0};
         ws();
         if (p >= end) return fail();
         if (*p != '{') {
+            rec.flags = kPersonNotObject;
             if (!skip(2)) return false;
             arena->persons.push_back(rec);
             return true;
@@ -363,8 +372,10 @@ struct Parser {
         if (p >= end) return fail();
         arena->persons.resize(people_first);                // a repeated "people" key overrides
         people_count = 0;
+        file_flags &= (int8_t)~(kFilePeopleNull | kFilePeopleOther);
         if (*p != '[') {
             have_people = false;
+            file_flags |= *p == 'n' ? kFilePeopleNull : kFilePeopleOther;
             return skip(1);
         }
         have_people = true;
@@ -398,6 +409,7 @@ struct Parser {
         bool is_object = false;
         if (p < end && *p == '{') {
             is_object = true;
+            file_flags |= kFileTopObject;
             ++p;
             ws();
             if (p < end && *p == '}') {
@@ -557,6 +569,7 @@ int p2s_json_parse(const char *paths, const int64_t *path_offsets, int64_t n_fil
                 fr.thread = t;
                 fr.first_person = (int64_t)arena.persons.size();
                 fr.count = P2S_JSON_UNREADABLE;
+                fr.flags = 0;
                 const int64_t len = path_offsets[i + 1] - path_offsets[i];
                 if (len <= 0) continue;                                     // no file for this slot
                 path.assign(paths + path_offsets[i], (size_t)len);
@@ -568,6 +581,7 @@ int p2s_json_parse(const char *paths, const int64_t *path_offsets, int64_t n_fil
                 ps.end = ps.p + n;
                 ps.arena = &arena;
                 fr.count = ps.document();
+                fr.flags = ps.file_flags;
             }
         });
         b->person_base.resize((size_t)n_files + 1);
@@ -795,6 +809,106 @@ int p2s_json_gather_largest_person(const p2s_json_batch *b, const int32_t *keypo
                 for (int64_t k = 0; k < (int64_t)n_ids * 3; ++k) dst[k] = nan;   // the except branch: all NaN
         }
     });
+    return P2S_OK;
+}
+
+// np.add.reduce over a contiguous float64 vector of fewer than 128 entries (NumPy's pairwise_sum): a plain loop below 8
+// entries, otherwise eight running sums over the whole blocks of eight, combined as a tree, then the tail one by one.
+static double numpy_sum_below_128(const double *a, int n) {
+    if (n < 8) {
+        double r = 0.0;
+        for (int i = 0; i < n; ++i) r += a[i];
+        return r;
+    }
+    double r[8];
+    for (int j = 0; j < 8; ++j) r[j] = a[j];
+    int i = 8;
+    for (; i < n - (n % 8); i += 8)
+        for (int j = 0; j < 8; ++j) r[j] += a[i + j];
+    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; ++i) res += a[i];
+    return res;
+}
+
+int p2s_json_select_tracked_person(const p2s_json_batch *b, int32_t n_kpts, double conf_threshold, double *out,
+                                   int32_t *status, int32_t *detail) {
+#pragma clang fp contract(off)                                   // dx*dx + dy*dy as NumPy rounds it: no FMA
+    if (!b || (b->n_files > 0 && (!out || !status))) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
+    if (n_kpts < 1 || n_kpts > 127) return p2s_set_error(P2S_ERR_INVALID_ARG, "n_kpts=%d outside [1, 127]", n_kpts);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const int32_t need = 3 * n_kpts;
+    const double *prev = nullptr;                                 // the last selection (prev_kp): it lives in an arena
+    std::vector<int32_t> cand;
+    std::vector<double> dist((size_t)n_kpts);
+    auto valid = [&](const double *v, int k) { return v[3 * k + 2] > conf_threshold && !(v[3 * k] != v[3 * k]); };
+    for (int64_t i = 0; i < b->n_files; ++i) {
+        double *dst = out + i * (int64_t)need;
+        for (int32_t k = 0; k < need; ++k) dst[k] = nan;
+        if (detail) detail[i] = 0;
+        const FileRec &fr = b->files[(size_t)i];
+        if (fr.count == P2S_JSON_UNREADABLE) { status[i] = P2S_TRACK_BAD_FILE; continue; }
+        if (fr.count == P2S_JSON_NO_PEOPLE_LIST) {
+            const bool none = (fr.flags & kFileTopObject) && !(fr.flags & kFilePeopleOther);   // data.get('people', []) is falsy
+            status[i] = none ? P2S_TRACK_NO_PEOPLE : P2S_TRACK_BAD_CONTENT;
+            continue;
+        }
+        if (fr.count == 0) { status[i] = P2S_TRACK_NO_PEOPLE; continue; }
+        const Arena &arena = b->arenas[(size_t)fr.thread];
+        // the reference visits every person before it chooses: the first offending one ends the run
+        cand.clear();
+        int32_t bad = 0;
+        for (int32_t n = 0; n < fr.count && !bad; ++n) {
+            const Person &ps = arena.persons[(size_t)(fr.first_person + n)];
+            if ((ps.flags & kPersonNotObject) || ps.status == kPersonBadList || ps.status == kPersonNonNumeric || (ps.flags & kPersonHasNull)) {
+                bad = P2S_TRACK_BAD_CONTENT;
+            } else if (ps.status == kPersonOk && ps.len > need) {
+                bad = P2S_TRACK_LONG_LIST;
+                if (detail) detail[i] = ps.len;
+            } else if (ps.status == kPersonOk && ps.len == need) {
+                const double *v = arena.values.data() + ps.off;
+                bool any = false;
+                for (int k = 0; k < n_kpts && !any; ++k) any = valid(v, k);
+                if (any) cand.push_back(n);
+            }                                                     // a short or missing list: skipped
+        }
+        if (bad) { status[i] = bad; continue; }
+        if (cand.empty()) { status[i] = P2S_TRACK_NO_CANDIDATE; continue; }
+        auto values_of = [&](int32_t n) { return arena.values.data() + arena.persons[(size_t)(fr.first_person + n)].off; };
+        int32_t chosen = -1;
+        if (cand.size() == 1) {
+            chosen = cand[0];
+        } else {
+            if (prev) {                                           // a selection always has a non-NaN x: never all NaN
+                double best = std::numeric_limits<double>::infinity();
+                for (int32_t n : cand) {
+                    const double *v = values_of(n);
+                    int m = 0;
+                    for (int k = 0; k < n_kpts; ++k) {
+                        if (!valid(v, k) || !valid(prev, k)) continue;
+                        const double dx = v[3 * k] - prev[3 * k], dy = v[3 * k + 1] - prev[3 * k + 1];
+                        dist[(size_t)m++] = std::sqrt(dx * dx + dy * dy);
+                    }
+                    if (m == 0) continue;
+                    const double mean = numpy_sum_below_128(dist.data(), m) / (double)m;
+                    if (mean < best) { best = mean; chosen = n; }  // strictly smaller; NaN and inf never win
+                }
+            }
+            if (chosen < 0) {                                     // the most confidences above the threshold, the first on ties
+                int most = -1;
+                for (int32_t n : cand) {
+                    const double *v = values_of(n);
+                    int cnt = 0;
+                    for (int k = 0; k < n_kpts; ++k) cnt += v[3 * k + 2] > conf_threshold;
+                    if (cnt > most) { most = cnt; chosen = n; }
+                }
+            }
+        }
+        const double *v = values_of(chosen);
+        for (int32_t k = 0; k < need; ++k) dst[k] = v[k];
+        prev = v;
+        status[i] = P2S_TRACK_SELECTED;
+        if (detail) detail[i] = chosen;
+    }
     return P2S_OK;
 }
 

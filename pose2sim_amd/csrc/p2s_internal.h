@@ -267,4 +267,46 @@ struct P2sReprojArgs {
 };
 hipError_t p2s_launch_reproject(const P2sReprojArgs &a, hipStream_t s);
 
+// p2s_jitter.hip: exact order statistics of fp64 columns, NaN skipped (np.nanmedian and its kin)
+struct P2sOrderArgs {
+    const double *data;
+    const int64_t *col_off;      // [n_cols] first element of every column, or NULL: col * n_rows
+    const int64_t *col_len;      // [n_cols] length of every column, or NULL: n_rows
+    const int64_t *ranks;        // [n_ranks] 0-based ranks among the non-NaN entries, negative = from the top; NULL: the
+                                 // two middle positions (m - 1) / 2 and m / 2 of every column (n_ranks is taken as 2)
+    double *out;                 // [n_cols][n_ranks]; NaN for a rank outside [0, m)
+    int64_t *counts;             // [n_cols] non-NaN entries m, or NULL
+    int64_t n_rows;
+    int32_t n_cols, n_ranks;
+};
+hipError_t p2s_launch_order_stats(const P2sOrderArgs &a, hipStream_t s);
+
+// p2s_jitter.hip: 2D keypoint jitter analysis (Utilities/keypoint_jitter_analyze.py:143-325).  Cameras back to back:
+// camera c holds frames frame_off[c] .. frame_off[c + 1] and one displacement row fewer than frames, so its first row
+// among all rows is frame_off[c] - c.
+#define P2S_JITTER_KPTS 26
+struct P2sJitterArgs {
+    const double *series;        // [frames][26][3] (x, y, confidence)
+    const int64_t *frame_off;    // [C + 1]
+    const int64_t *tile_base;    // [C + 1] first 256-row tile of every camera
+    double *disp;                // per camera [26][rows]: column-major, for the order statistics
+    double *area;                // [frames] box area, NaN with fewer than 2 valid keypoints
+    uint8_t *edge;               // [frames] 1: the box comes within 10 px of the image border
+    const double *stats;         // [C][27][2] the two middle values of the 26 displacement columns and the area column
+    const int64_t *stat_counts;  // [C][27] their non-NaN counts
+    double *medians, *thresholds;   // [C][26]
+    double *med_area;            // [C]
+    uint8_t *mask;               // [rows][26]
+    int32_t *counts;             // [C][26] events per keypoint (zeroed by the caller)
+    uint32_t *tile_count;        // [n_tiles]
+    long long *tile_off;         // [n_tiles] exclusive scan of tile_count
+    long long *n_events;
+    int32_t *events;             // [event_capacity][4] camera, frame, keypoint, pattern (0 A, 1 C, 2 D, 3 E)
+    int64_t event_capacity;
+    int64_t n_tiles, max_frames;
+    double multiplier, x_edge, y_edge;   // width - 10, height - 10
+    int32_t C;
+};
+hipError_t p2s_launch_jitter(const P2sJitterArgs &a, const P2sOrderArgs &o, hipStream_t s);
+
 #endif

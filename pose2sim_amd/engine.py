@@ -349,6 +349,74 @@ class Engine:
     def write_openpose_files(self, cam_dirs, name_root, uv, marker_index=None, n_threads=0):
         return write_openpose_files(cam_dirs, name_root, uv, marker_index, n_threads)
 
+    # -- exact order statistics; 2D keypoint jitter (Utilities/keypoint_jitter_analyze.py:143-325) -------------------------
+    def column_order_stats(self, data, ranks):
+        """data [n_rows][n_cols] float64 (any strides; NaN entries are skipped), ranks: 0-based positions among each
+        column's sorted non-NaN entries, negative = from the top.  -> (values [n_cols][n_ranks], NaN where the rank is
+        outside the column's count; counts [n_cols] of non-NaN entries).  Exact: a radix select on the bit patterns."""
+        if not hasattr(self._lib, 'p2s_column_order_stats_host'):
+            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_column_order_stats_host: rebuild it')
+        data = np.asarray(data, dtype=np.float64)
+        if data.ndim != 2:
+            raise P2sError(f'data has shape {data.shape}; expected [n_rows][n_cols]')
+        cols = np.ascontiguousarray(data.T)                       # the library takes the columns contiguous
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        n_cols, n_rows = cols.shape
+        out = np.empty((n_cols, len(ranks)))
+        counts = np.zeros(n_cols, dtype=np.int64)
+        _lib.check(self._lib.p2s_column_order_stats_host(self._h, n_rows, n_cols, _ptr(cols) if cols.size else None, len(ranks),
+                                                         _ptr(ranks) if ranks.size else None, _ptr(out) if out.size else None,
+                                                         _ptr(counts) if n_cols else None))
+        return out, counts
+
+    def jitter(self, series, multiplier=5.0, image_size=(1920, 1080)):
+        """series: one [n_frames][26][3] (x, y, confidence) float64 array per camera (lengths may differ, each >= 1).
+        -> dict: per camera (lists) 'displacements' [F-1][26] (a transposed view of the keypoint-major table the kernels
+        keep), 'bb_areas' [F], 'jitter_mask' [F-1][26] bool, 'medians', 'thresholds' [26], 'median_bb_area', 'counts' [26];
+        and 'events' [n][4] int32 (camera, frame, keypoint, pattern 0 A / 1 C / 2 D / 3 E) for all cameras, in the
+        reference's order."""
+        if not hasattr(self._lib, 'p2s_jitter_host'):
+            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_jitter_host: rebuild it')
+        series = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+        for s in series:
+            if s.ndim != 3 or s.shape[1:] != (26, 3) or len(s) < 1:
+                raise P2sError(f'a series has shape {s.shape}; expected [n_frames >= 1][26][3]')
+        Cn = len(series)
+        n_frames = np.array([len(s) for s in series], dtype=np.int64)
+        flat = series[0] if Cn == 1 else np.concatenate(series)
+        frames, rows = int(n_frames.sum()), int(n_frames.sum()) - Cn
+        disp, areas = np.empty(rows * 26), np.empty(frames)
+        med, thr, med_area = np.empty((Cn, 26)), np.empty((Cn, 26)), np.empty(Cn)
+        mask, counts = np.empty((rows, 26), dtype=np.uint8), np.zeros((Cn, 26), dtype=np.int32)
+        capacity = min(max(rows, 1) * 26, 1 << 18)
+        while True:
+            events, found = np.empty((capacity, 4), dtype=np.int32), C.c_int64(0)
+            _lib.check(self._lib.p2s_jitter_host(self._h, Cn, _ptr(n_frames), _ptr(flat), float(multiplier), float(image_size[0]),
+                                                 float(image_size[1]), _ptr(disp) if rows else None, _ptr(areas), _ptr(med), _ptr(thr),
+                                                 _ptr(med_area), _ptr(mask) if rows else None, _ptr(counts), capacity, _ptr(events),
+                                                 C.byref(found)))
+            if found.value <= capacity:
+                break
+            capacity = found.value                                # a second call with room for every event
+        f_off = np.concatenate([[0], np.cumsum(n_frames)])
+        r_off = f_off - np.arange(Cn + 1)
+        out = {'displacements': [], 'bb_areas': [], 'jitter_mask': [], 'medians': list(med), 'thresholds': list(thr),
+               'median_bb_area': [float(v) for v in med_area], 'counts': list(counts), 'events': events[:found.value]}
+        for c in range(Cn):
+            R = int(n_frames[c]) - 1
+            out['displacements'].append(disp[26 * r_off[c]:26 * r_off[c + 1]].reshape(26, R).T)
+            out['bb_areas'].append(areas[f_off[c]:f_off[c + 1]])
+            out['jitter_mask'].append(mask[r_off[c]:r_off[c + 1]].view(np.bool_))
+        return out
+
+    def jitter_kernel_ms(self):
+        """Kernel time of the last jitter() call, from HIP events around its kernels."""
+        if not hasattr(self._lib, 'p2s_jitter_kernel_ms'):
+            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_jitter_kernel_ms: rebuild it')
+        ms = C.c_float(0)
+        _lib.check(self._lib.p2s_jitter_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
     # -- synchronization (synchronization.py:1271-1343, 1541-1585) -------------------------------------------------------
     def sync_speeds(self, coords, b, a, zi):
         """coords: one [n_frames][n_cols] array per camera, the (x, y) columns of the keypoints to consider with the

@@ -100,6 +100,18 @@ class JsonBatch:
                                                             _ptr(out)))
         return out
 
+    def select_tracked_person(self, n_kpts=26, conf_threshold=0.1):
+        """load_keypoints_series / _select_person (Utilities/keypoint_jitter_analyze.py:50-140) over the files in order:
+        -> (series [n_files][n_kpts][3], status [n_files] P2S_TRACK_*, detail [n_files]); see p2s_json_select_tracked_person."""
+        if not hasattr(self._lib, 'p2s_json_select_tracked_person'):
+            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_json_select_tracked_person: rebuild it')
+        out = np.empty((self.n_files, int(n_kpts), 3), dtype=np.float64)
+        status = np.zeros(self.n_files, dtype=np.int32)
+        detail = np.zeros(self.n_files, dtype=np.int32)
+        _lib.check(self._lib.p2s_json_select_tracked_person(self._h, int(n_kpts), float(conf_threshold), _ptr(out), _ptr(status),
+                                                            _ptr(detail)))
+        return out, status, detail
+
 
 def copy_files(pairs, n_threads=0):
     """shutil.copy(src, dst) for every (src, dst) pair on host threads (p2s_copy_files); raises OSError on a failure."""
