@@ -17,8 +17,71 @@
 #include <stdint.h>
 #include <math.h>
 
-#include "p2s_internal.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "p2s_ctx.h"
 #include "p2s_iir.h"
+
+struct P2sFilterArgs {
+    const double *in;            // [n_frames][n_cols]
+    double *out;                 // [n_frames][n_cols]
+    double *work;                // [n_frames + 2 padlen][n_cols] forward-pass output
+    int64_t n_frames;
+    int32_t n_cols, n_order, padlen;   // n_order = len(b) - 1
+    double b[P2S_MAX_FILTER_ORDER + 1], a[P2S_MAX_FILTER_ORDER + 1], zi[P2S_MAX_FILTER_ORDER];
+};
+
+// the window filters (Hampel, Gaussian, median) and the one-euro recurrence of filtering.py
+struct P2sColFilterArgs {
+    const double *in;            // [n_frames][n_cols]
+    double *out;                 // [n_frames][n_cols]
+    double *work;                // one-euro: forward pass [n_frames][n_cols]
+    const double *w;             // Gaussian: 2 radius + 1 weights (device)
+    int64_t n_frames;
+    int32_t n_cols, kind, radius;
+    double p[4];                 // Hampel: n_sigma; one-euro: dt, min_cutoff, beta, d_cutoff
+};
+
+// gcv_spline_filter_1d: one lane per run of >= 5 valid samples.  The host sorts the runs longest first; run r is lane
+// r % 64 of wave r / 64, whose factor storage starts at work_off doubles into `work`: [sample][P2S_GCV_SLOTS][64 lanes]
+// over the wave's longest run.
+#define P2S_GCV_SLOTS 11
+#define P2S_GCV_OK 0
+#define P2S_GCV_ILL_POSED 1          // the banded Cholesky factorisation failed (scipy: 'Seems like the problem is ill-posed')
+#define P2S_GCV_MAX_EVALS 2          // minimize_scalar stopped at maxiter = 500 evaluations
+#define P2S_GCV_NAN 3                // minimize_scalar met a NaN
+#define P2S_GCV_SINGULAR 4           // a zero pivot in the banded LU solve (LAPACK gbsv info > 0)
+struct P2sGcvRun {
+    int64_t work_off;            // doubles into P2sGcvArgs::work of this run's wave
+    int32_t col, start, len;     // column, first frame, number of samples (>= 5)
+    int32_t n_eval;              // out: GCV evaluations of the search ('auto')
+    double med, scale;           // 'auto': the run's median and 1.4826 * MAD (MAD 0 -> 1)
+    double lam;                  // out: the lambda of the final fit
+    int32_t status, pad;         // out: P2S_GCV_*
+};
+struct P2sGcvArgs {
+    double *data;                // [n_frames][n_cols]: read, and the filtered runs written in place
+    P2sGcvRun *runs;             // [n_runs]
+    double *work;
+    int64_t n_frames;
+    int32_t n_cols, n_runs;
+    int32_t auto_mode;           // 1: GCV search of lambda on the normalised run; 0: lambda = fixed_lam on the raw run
+    double fixed_lam, smoothing_factor;
+};
+
+struct P2sMetricsArgs {
+    const double *xyz;           // [n_frames][n_markers][3]
+    const int32_t *bones;        // [n_bones][2] (parent, child) marker indices
+    double *bone_len;            // [n_bones][n_frames]
+    double *bone_stats;          // [n_bones][3] mean, population sd, n_valid
+    double *accel;               // [n_markers][n_frames - 2]
+    int64_t *missing;            // [n_markers]
+    int64_t n_frames;
+    int32_t n_markers, n_bones;
+};
 
 namespace {
 
@@ -749,7 +812,7 @@ __global__ void __launch_bounds__(64) p2s_gcv_spline_kernel(const P2sGcvArgs a) 
 
 }  // namespace
 
-hipError_t p2s_launch_butter(const P2sFilterArgs &a, hipStream_t s) {
+static hipError_t p2s_launch_butter(const P2sFilterArgs &a, hipStream_t s) {
     const unsigned grid = (unsigned)((a.n_cols + 63) / 64);
     switch (a.n_order) {
     case 1: hipLaunchKernelGGL((p2s_butter_kernel<1>), dim3(grid), dim3(64), 0, s, a); break;
@@ -765,7 +828,7 @@ hipError_t p2s_launch_butter(const P2sFilterArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t p2s_launch_col_filter(const P2sColFilterArgs &a, hipStream_t s) {
+static hipError_t p2s_launch_col_filter(const P2sColFilterArgs &a, hipStream_t s) {
     const int64_t total = a.n_frames * a.n_cols;
     if (total == 0) return hipSuccess;
     const unsigned grid_e = (unsigned)((total + 255) / 256), grid_c = (unsigned)((a.n_cols + 63) / 64);
@@ -780,16 +843,239 @@ hipError_t p2s_launch_col_filter(const P2sColFilterArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t p2s_launch_trc_metrics(const P2sMetricsArgs &a, hipStream_t s) {
-    const unsigned grid = (unsigned)(a.n_bones + a.n_markers);
-    if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(p2s_trc_metrics_kernel, dim3(grid), dim3(256), 0, s, a);
-    return hipGetLastError();
+// ---- C-ABI entry points (include/p2s.h) ----------------------------------------------------------------------------
+namespace {
+
+// np.median of v (destroyed): the middle order statistic, or the mean of the two middle ones
+double median_of(std::vector<double> &v) {
+    const size_t n = v.size(), h = n / 2;
+    std::nth_element(v.begin(), v.begin() + h, v.end());
+    const double hi = v[h];
+    if (n % 2) return hi;
+    const double lo = *std::max_element(v.begin(), v.begin() + h);
+    return (lo + hi) / 2.0;
 }
 
-hipError_t p2s_launch_gcv_spline(const P2sGcvArgs &a, hipStream_t s) {
-    if (a.n_runs == 0) return hipSuccess;
-    const unsigned grid = (unsigned)((a.n_runs + 63) / 64);
-    hipLaunchKernelGGL(p2s_gcv_spline_kernel, dim3(grid), dim3(64), 0, s, a);
-    return hipGetLastError();
+}  // namespace
+
+extern "C" {
+
+int p2s_butterworth_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const double *data, int32_t n_coef,
+                         const double *b, const double *a, const double *zi, double *out) {
+    if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
+    if (n_frames < 0 || n_cols < 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "bad shape: n_frames=%lld n_cols=%d", (long long)n_frames, n_cols);
+    if (n_coef < 2 || n_coef > P2S_MAX_FILTER_ORDER + 1)
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "filter with %d coefficients: supported 2..%d", n_coef, P2S_MAX_FILTER_ORDER + 1);
+    if (n_frames == 0 || n_cols == 0) return P2S_OK;
+    if (!data || !out || !b || !a || !zi) return p2s_set_error(P2S_ERR_INVALID_ARG, "null pointer");
+    if (!(a[0] == 1.0)) return p2s_set_error(P2S_ERR_INVALID_ARG, "a[0] must be 1 (scipy.signal.butter normalises it)");
+    P2sFilterArgs f{};
+    f.n_frames = n_frames; f.n_cols = n_cols; f.n_order = n_coef - 1;
+    f.padlen = 3 * n_coef;                                  // filtering.py:457
+    for (int i = 0; i < n_coef; ++i) { f.b[i] = b[i]; f.a[i] = a[i]; }
+    for (int i = 0; i < n_coef - 1; ++i) f.zi[i] = zi[i];
+    const size_t bytes = (size_t)n_frames * n_cols * sizeof(double);
+    HIP_TRY(hipSetDevice(ctx->device));
+    Stage st{ctx};
+    P2S_TRY(st.upload(f.in, data, bytes));
+    P2S_TRY(st.alloc(f.out, bytes));
+    P2S_TRY(st.alloc(f.work, (size_t)(n_frames + 2 * f.padlen) * n_cols * sizeof(double)));
+    HIP_TRY(p2s_launch_butter(f, ctx->stream));
+    P2S_TRY(st.down(out, f.out, bytes));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return P2S_OK;
 }
+
+int p2s_filter_columns_host(p2s_ctx *ctx, int32_t kind, int64_t n_frames, int32_t n_cols, const double *data,
+                            const double *params, int32_t n_params, double *out) {
+    if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
+    if (n_frames < 0 || n_cols < 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "bad shape: n_frames=%lld n_cols=%d", (long long)n_frames, n_cols);
+    if (n_params < 0 || (n_params > 0 && !params)) return p2s_set_error(P2S_ERR_INVALID_ARG, "null parameters");
+    P2sColFilterArgs f{};
+    f.kind = kind; f.n_frames = n_frames; f.n_cols = n_cols;
+    switch (kind) {
+    case P2S_FILTER_HAMPEL:
+        if (n_params != 1) return p2s_set_error(P2S_ERR_INVALID_ARG, "Hampel filter: params = {n_sigma}");
+        f.p[0] = params[0];
+        break;
+    case P2S_FILTER_GAUSSIAN:
+        if (n_params < 1 || n_params % 2 != 1 || n_params > 8191) return p2s_set_error(P2S_ERR_INVALID_ARG, "Gaussian filter: params = 2 radius + 1 weights");
+        f.radius = n_params / 2;
+        break;
+    case P2S_FILTER_MEDIAN: {
+        if (n_params != 1) return p2s_set_error(P2S_ERR_INVALID_ARG, "median filter: params = {kernel_size}");
+        const int k = (int)params[0];
+        if ((double)k != params[0] || k < 1 || k % 2 != 1 || k > 1023) return p2s_set_error(P2S_ERR_INVALID_ARG, "median filter: kernel_size must be odd, 1..1023");
+        f.radius = k / 2;
+        break;
+    }
+    case P2S_FILTER_ONE_EURO:
+        if (n_params != 4) return p2s_set_error(P2S_ERR_INVALID_ARG, "one-euro filter: params = {dt, min_cutoff, beta, d_cutoff}");
+        for (int i = 0; i < 4; ++i) f.p[i] = params[i];
+        if (!(f.p[0] > 0.0)) return p2s_set_error(P2S_ERR_INVALID_ARG, "one-euro filter: dt must be positive");
+        break;
+    case P2S_FILTER_KALMAN:
+        if (n_params != 4) return p2s_set_error(P2S_ERR_INVALID_ARG, "Kalman filter: params = {dt, measurement_noise, process_noise, smooth}");
+        for (int i = 0; i < 4; ++i) f.p[i] = params[i];
+        if (!(f.p[0] > 0.0)) return p2s_set_error(P2S_ERR_INVALID_ARG, "Kalman filter: dt must be positive");
+        break;
+    default: return p2s_set_error(P2S_ERR_INVALID_ARG, "unknown column filter %d", kind);
+    }
+    if (n_frames == 0 || n_cols == 0) return P2S_OK;
+    if (!data || !out) return p2s_set_error(P2S_ERR_INVALID_ARG, "null pointer");
+    const size_t bytes = (size_t)n_frames * n_cols * sizeof(double);
+    if (kind == P2S_FILTER_MEDIAN)
+        for (size_t i = 0, n = (size_t)n_frames * n_cols; i < n; ++i)
+            if (!(data[i] == data[i])) return p2s_set_error(P2S_ERR_INVALID_ARG, "median filter: the data hold NaN (scipy.signal.medfilt's answer for them is not defined)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    Stage st{ctx};
+    P2S_TRY(st.upload(f.in, data, bytes));
+    P2S_TRY(st.alloc(f.out, bytes));
+    if (kind == P2S_FILTER_ONE_EURO || kind == P2S_FILTER_KALMAN) P2S_TRY(st.alloc(f.work, kind == P2S_FILTER_KALMAN ? 12 * bytes : bytes));
+    if (kind == P2S_FILTER_GAUSSIAN) P2S_TRY(st.upload(f.w, params, (size_t)n_params * sizeof(double)));
+    HIP_TRY(p2s_launch_col_filter(f, ctx->stream));
+    P2S_TRY(st.down(out, f.out, bytes));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return P2S_OK;
+}
+
+int p2s_gcv_spline_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const double *data, int32_t auto_mode,
+                        double lam, double smoothing_factor, double *out, double *lam_out) {
+    if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
+    if (n_frames < 0 || n_frames > INT32_MAX || n_cols < 0)
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "bad shape: n_frames=%lld n_cols=%d", (long long)n_frames, n_cols);
+    if (n_frames == 0 || n_cols == 0) return P2S_OK;
+    if (!data || !out) return p2s_set_error(P2S_ERR_INVALID_ARG, "null pointer");
+    const int64_t S = n_cols;
+    const size_t total = (size_t)n_frames * n_cols;
+    std::memcpy(out, data, total * sizeof(double));
+    if (lam_out)
+        for (size_t i = 0; i < total; ++i) lam_out[i] = NAN;
+
+    // the runs of valid samples (neither NaN nor 0, filtering.py:265-270), column by column
+    std::vector<P2sGcvRun> runs;
+    std::vector<double> tmp;
+    for (int32_t c = 0; c < n_cols; ++c) {
+        int64_t f = 0;
+        while (f < n_frames) {
+            auto valid = [&](int64_t i) { const double v = data[i * S + c]; return v == v && v != 0.0; };
+            if (!valid(f)) { ++f; continue; }
+            int64_t r = f + 1;
+            while (r < n_frames && valid(r)) ++r;
+            const int64_t len = r - f;
+            if (len >= 2 && len <= 4)                      // make_smoothing_spline / the GCV helper refuse n <= 4
+                return p2s_set_error(P2S_ERR_GCV_SHORT_RUN, "``x`` and ``y`` length must be at least 5");
+            if (len >= 5) {
+                P2sGcvRun run{};
+                run.col = c; run.start = (int32_t)f; run.len = (int32_t)len;
+                run.med = 0.0; run.scale = 1.0;
+                for (int64_t i = f; i < r; ++i)
+                    if (std::isinf(data[i * S + c])) return p2s_set_error(P2S_ERR_INVALID_ARG, "array must not contain infs or NaNs");
+                if (auto_mode) {                           // filtering.py:277-281
+                    tmp.assign(len, 0.0);
+                    for (int64_t i = 0; i < len; ++i) tmp[i] = data[(f + i) * S + c];
+                    const double med = median_of(tmp);
+                    for (int64_t i = 0; i < len; ++i) tmp[i] = std::fabs(data[(f + i) * S + c] - med);
+                    double mad = median_of(tmp);
+                    mad = mad > 0 ? mad : 1.0;
+                    run.med = med;
+                    run.scale = 1.4826 * mad;
+                }
+                runs.push_back(run);
+            }
+            f = r;
+        }
+    }
+    if (runs.empty()) return P2S_OK;
+    if (!((auto_mode ? smoothing_factor : lam * smoothing_factor) >= 0.0))
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "Regularization parameter should be non-negative");
+
+    // longest first, so that the long runs start first and a wave's lanes have similar lengths; the factor storage of
+    // a wave covers its longest run
+    std::vector<int32_t> order(runs.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = (int32_t)i;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return runs[x].len > runs[y].len; });
+    std::vector<P2sGcvRun> sorted(runs.size());
+    size_t work_doubles = 0;
+    for (size_t i = 0; i < order.size(); ++i) {
+        sorted[i] = runs[order[i]];
+        if (i % 64 == 0) {
+            sorted[i].work_off = (int64_t)work_doubles;
+            work_doubles += (size_t)sorted[i].len * P2S_GCV_SLOTS * 64;
+        } else {
+            sorted[i].work_off = sorted[i - i % 64].work_off;
+        }
+    }
+
+    P2sGcvArgs g{};
+    g.n_frames = n_frames; g.n_cols = n_cols; g.n_runs = (int32_t)sorted.size();
+    g.auto_mode = auto_mode ? 1 : 0;
+    g.fixed_lam = lam * smoothing_factor;                  // filtering.py:301-304
+    g.smoothing_factor = smoothing_factor;
+    const size_t bytes = total * sizeof(double), run_bytes = sorted.size() * sizeof(P2sGcvRun);
+    HIP_TRY(hipSetDevice(ctx->device));
+    Stage st{ctx};
+    P2S_TRY(st.upload(g.data, data, bytes));
+    P2S_TRY(st.upload(g.runs, sorted.data(), run_bytes));
+    P2S_TRY(st.alloc(g.work, work_doubles * sizeof(double)));
+    hipLaunchKernelGGL(p2s_gcv_spline_kernel, dim3((unsigned)((g.n_runs + 63) / 64)), dim3(64), 0, ctx->stream, g);
+    HIP_TRY(hipGetLastError());
+    P2S_TRY(st.down(out, g.data, bytes));
+    P2S_TRY(st.down(sorted.data(), g.runs, run_bytes));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+
+    // the reference stops at the first run (column by column) whose search or solve fails
+    const P2sGcvRun *bad = nullptr;
+    for (const P2sGcvRun &r : sorted)
+        if (r.status != P2S_GCV_OK && (!bad || r.col < bad->col || (r.col == bad->col && r.start < bad->start))) bad = &r;
+    if (bad) {
+        std::memcpy(out, data, bytes);
+        switch (bad->status) {
+        case P2S_GCV_ILL_POSED: return p2s_set_error(P2S_ERR_GCV_ILL_POSED, "Seems like the problem is ill-posed");
+        case P2S_GCV_SINGULAR: return p2s_set_error(P2S_ERR_GCV_SINGULAR, "singular matrix");
+        case P2S_GCV_MAX_EVALS:
+            return p2s_set_error(P2S_ERR_GCV_NO_MINIMUM, "Unable to find minimum of the GCV function: Maximum number of function calls reached.");
+        default: return p2s_set_error(P2S_ERR_GCV_NO_MINIMUM, "Unable to find minimum of the GCV function: NaN result encountered.");
+        }
+    }
+    if (lam_out)
+        for (const P2sGcvRun &r : sorted) lam_out[(int64_t)r.start * S + r.col] = r.lam;
+    return P2S_OK;
+}
+
+int p2s_trc_metrics_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_markers, const double *xyz, int32_t n_bones,
+                         const int32_t *bones, double *bone_len, double *bone_stats, double *accel, int64_t *missing) {
+    if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
+    if (n_frames < 0 || n_markers < 0 || n_bones < 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "bad shape");
+    if (n_frames == 0 || (n_markers == 0 && n_bones == 0)) return P2S_OK;
+    if (!xyz || (n_bones && (!bones || !bone_len || !bone_stats)) || (n_markers && (!accel || !missing)))
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "null pointer");
+    for (int i = 0; i < 2 * n_bones; ++i)
+        if (bones[i] < 0 || bones[i] >= n_markers) return p2s_set_error(P2S_ERR_INVALID_ARG, "bone %d names marker %d of %d", i / 2, bones[i], n_markers);
+    const size_t xyz_b = (size_t)n_frames * n_markers * 3 * sizeof(double);
+    const size_t len_b = (size_t)n_bones * n_frames * sizeof(double);
+    const size_t acc_b = (size_t)n_markers * (n_frames > 2 ? n_frames - 2 : 0) * sizeof(double);
+    HIP_TRY(hipSetDevice(ctx->device));
+    P2sMetricsArgs m{};
+    m.n_frames = n_frames; m.n_markers = n_markers; m.n_bones = n_bones;
+    Stage st{ctx};
+    unsigned char *aux;                                    // one block: bones [n_bones][2] i32, bone_stats [n_bones][3], missing [n_markers]
+    P2S_TRY(st.upload(m.xyz, xyz, xyz_b));
+    P2S_TRY(st.alloc(m.bone_len, len_b));
+    P2S_TRY(st.alloc(m.accel, acc_b));
+    P2S_TRY(st.alloc(aux, (size_t)n_bones * 32 + (size_t)n_markers * 8));
+    m.bones = (const int32_t *)aux;
+    m.bone_stats = (double *)(aux + (size_t)n_bones * 8);
+    m.missing = (int64_t *)(aux + (size_t)n_bones * 32);
+    P2S_TRY(st.up(aux, bones, (size_t)n_bones * 8));
+    hipLaunchKernelGGL(p2s_trc_metrics_kernel, dim3((unsigned)(n_bones + n_markers)), dim3(256), 0, ctx->stream, m);
+    HIP_TRY(hipGetLastError());
+    P2S_TRY(st.down(bone_len, m.bone_len, len_b));
+    P2S_TRY(st.down(bone_stats, m.bone_stats, (size_t)n_bones * 24));
+    P2S_TRY(st.down(accel, m.accel, acc_b));
+    P2S_TRY(st.down(missing, m.missing, (size_t)n_markers * 8));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return P2S_OK;
+}
+
+}  // extern "C"

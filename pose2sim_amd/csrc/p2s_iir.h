@@ -5,6 +5,8 @@
 
 #include <hip/hip_runtime.h>
 
+#define P2S_MAX_FILTER_ORDER 8
+
 // One sample of scipy's lfilter (direct form II transposed, a[0] = 1): y = z[0] + b[0] x, then
 // z[k] = z[k+1] + b[k+1] x - a[k+1] y.  Same operation order as scipy's C loop and no contraction, so that the result
 // matches scipy.signal.filtfilt to rounding.  b, a: N + 1 coefficients.

@@ -26,8 +26,7 @@
 #include <unistd.h>
 
 #include "p2s.h"
-
-int p2s_set_error(int code, const char *fmt, ...);   // p2s_api.hip
+#include "p2s_error.h"
 
 namespace {
 

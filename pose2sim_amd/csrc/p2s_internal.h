@@ -1,4 +1,6 @@
-// Internal structures shared by the C-ABI layer (p2s_api.hip) and the kernels.
+// What more than one translation unit needs: the device-resident camera, the counter and work-list constants, and the
+// argument structs and launchers of the triangulation and association kernels, which p2s_api.hip drives.  The stages
+// downstream of the .trc keep their argument structs in their own .hip file, beside the kernels and the entry points.
 #ifndef P2S_INTERNAL_H
 #define P2S_INTERNAL_H
 
@@ -161,152 +163,5 @@ struct P2sSingleArgs {
 hipError_t p2s_launch_single(const P2sSingleArgs &a, int dtype, hipStream_t s);
 
 hipError_t p2s_launch_assoc(const P2sAssocArgs &a, int dtype, hipStream_t s);
-
-// p2s_filter.hip
-#define P2S_MAX_FILTER_ORDER 8
-struct P2sFilterArgs {
-    const double *in;            // [n_frames][n_cols]
-    double *out;                 // [n_frames][n_cols]
-    double *work;                // [n_frames + 2 padlen][n_cols] forward-pass output
-    int64_t n_frames;
-    int32_t n_cols, n_order, padlen;   // n_order = len(b) - 1
-    double b[P2S_MAX_FILTER_ORDER + 1], a[P2S_MAX_FILTER_ORDER + 1], zi[P2S_MAX_FILTER_ORDER];
-};
-hipError_t p2s_launch_butter(const P2sFilterArgs &a, hipStream_t s);
-
-// the window filters (Hampel, Gaussian, median) and the one-euro recurrence of filtering.py
-struct P2sColFilterArgs {
-    const double *in;            // [n_frames][n_cols]
-    double *out;                 // [n_frames][n_cols]
-    double *work;                // one-euro: forward pass [n_frames][n_cols]
-    const double *w;             // Gaussian: 2 radius + 1 weights (device)
-    int64_t n_frames;
-    int32_t n_cols, kind, radius;
-    double p[4];                 // Hampel: n_sigma; one-euro: dt, min_cutoff, beta, d_cutoff
-};
-hipError_t p2s_launch_col_filter(const P2sColFilterArgs &a, hipStream_t s);
-
-// gcv_spline_filter_1d: one lane per run of >= 5 valid samples.  The host sorts the runs longest first; run r is lane
-// r % 64 of wave r / 64, whose factor storage starts at work_off doubles into `work`: [sample][P2S_GCV_SLOTS][64 lanes]
-// over the wave's longest run.
-#define P2S_GCV_SLOTS 11
-#define P2S_GCV_OK 0
-#define P2S_GCV_ILL_POSED 1          // the banded Cholesky factorisation failed (scipy: 'Seems like the problem is ill-posed')
-#define P2S_GCV_MAX_EVALS 2          // minimize_scalar stopped at maxiter = 500 evaluations
-#define P2S_GCV_NAN 3                // minimize_scalar met a NaN
-#define P2S_GCV_SINGULAR 4           // a zero pivot in the banded LU solve (LAPACK gbsv info > 0)
-struct P2sGcvRun {
-    int64_t work_off;            // doubles into P2sGcvArgs::work of this run's wave
-    int32_t col, start, len;     // column, first frame, number of samples (>= 5)
-    int32_t n_eval;              // out: GCV evaluations of the search ('auto')
-    double med, scale;           // 'auto': the run's median and 1.4826 * MAD (MAD 0 -> 1)
-    double lam;                  // out: the lambda of the final fit
-    int32_t status, pad;         // out: P2S_GCV_*
-};
-struct P2sGcvArgs {
-    double *data;                // [n_frames][n_cols]: read, and the filtered runs written in place
-    P2sGcvRun *runs;             // [n_runs]
-    double *work;
-    int64_t n_frames;
-    int32_t n_cols, n_runs;
-    int32_t auto_mode;           // 1: GCV search of lambda on the normalised run; 0: lambda = fixed_lam on the raw run
-    double fixed_lam, smoothing_factor;
-};
-hipError_t p2s_launch_gcv_spline(const P2sGcvArgs &a, hipStream_t s);
-
-// p2s_sync.hip: synchronization speeds and their time-lagged Pearson correlation (synchronization.py:1271-1343, 1541-1575)
-struct P2sSyncArgs {
-    const double *coords;        // [total_rows][n_cols]: the cameras' masked (x, y) columns back to back
-    double *filled;              // [total_rows][n_cols]: interpolated, filled and filtered columns
-    double *work;                // [total_rows + 2 padlen n_cams][n_cols]: forward passes (camera c from row row0[c] + 2 padlen c)
-    double *speed;               // [total_rows]: sum of |vertical speeds|, then filtered in place
-    double *speed_work;          // [total_rows + 2 padlen n_cams]
-    const int64_t *row0;         // [n_cams + 1] first row of each camera
-    int64_t total_rows;
-    int32_t n_cams, n_cols, n_order, padlen;   // n_order = len(b) - 1; padlen = 3 len(b) (scipy's filtfilt)
-    int32_t filter_above;        // a camera is filtered when it has more frames than this (3 n_order, :1567)
-    double b[P2S_MAX_FILTER_ORDER + 1], a[P2S_MAX_FILTER_ORDER + 1], zi[P2S_MAX_FILTER_ORDER];
-};
-hipError_t p2s_launch_sync_speeds(const P2sSyncArgs &a, hipStream_t s);
-
-struct P2sPearsonArgs {
-    const double *ref;           // [n_ref]
-    const double *sig;           // the compared signals back to back
-    const int64_t *sig0;         // [n_sig + 1] offsets into sig
-    double *r;                   // [n_sig][n_lags]: r of lag lag_lo + t
-    int64_t *argmax;             // [n_sig]
-    double *max_corr;            // [n_sig]
-    int64_t n_ref, lag_lo, n_lags;
-    int32_t n_sig;
-};
-hipError_t p2s_launch_pearson(const P2sPearsonArgs &a, hipStream_t s);
-
-struct P2sMetricsArgs {
-    const double *xyz;           // [n_frames][n_markers][3]
-    const int32_t *bones;        // [n_bones][2] (parent, child) marker indices
-    double *bone_len;            // [n_bones][n_frames]
-    double *bone_stats;          // [n_bones][3] mean, population sd, n_valid
-    double *accel;               // [n_markers][n_frames - 2]
-    int64_t *missing;            // [n_markers]
-    int64_t n_frames;
-    int32_t n_markers, n_bones;
-};
-hipError_t p2s_launch_trc_metrics(const P2sMetricsArgs &a, hipStream_t s);
-
-// p2s_reproj.hip: 3D markers onto the image planes (Utilities/reproj_from_trc_calib.py:446-475)
-struct P2sReprojArgs {
-    const double *Q;             // [n_frames][K][3], Z-up (X, Y, Z); NaN = missing
-    const double *P;             // plain mode: [C][Fp][12]
-    const P2sCam *cams;          // distorted mode: [C] (R, T, fx, fy, cx, cy, k read); NULL = plain mode
-    const double *sizes;         // [C][2] width, height
-    double *uv_raw;              // [C][n_frames][K][2] unrounded pixels, or NULL
-    double *uv;                  // [C][n_frames][K][2] rounded to one decimal, NaN outside the image
-    int64_t n_units;             // n_frames * K
-    int64_t Fp;                  // 1, or n_frames: one projection matrix per frame
-    int32_t K, C;
-};
-hipError_t p2s_launch_reproject(const P2sReprojArgs &a, hipStream_t s);
-
-// p2s_jitter.hip: exact order statistics of fp64 columns, NaN skipped (np.nanmedian and its kin)
-struct P2sOrderArgs {
-    const double *data;
-    const int64_t *col_off;      // [n_cols] first element of every column, or NULL: col * n_rows
-    const int64_t *col_len;      // [n_cols] length of every column, or NULL: n_rows
-    const int64_t *ranks;        // [n_ranks] 0-based ranks among the non-NaN entries, negative = from the top; NULL: the
-                                 // two middle positions (m - 1) / 2 and m / 2 of every column (n_ranks is taken as 2)
-    double *out;                 // [n_cols][n_ranks]; NaN for a rank outside [0, m)
-    int64_t *counts;             // [n_cols] non-NaN entries m, or NULL
-    int64_t n_rows;
-    int32_t n_cols, n_ranks;
-};
-hipError_t p2s_launch_order_stats(const P2sOrderArgs &a, hipStream_t s);
-
-// p2s_jitter.hip: 2D keypoint jitter analysis (Utilities/keypoint_jitter_analyze.py:143-325).  Cameras back to back:
-// camera c holds frames frame_off[c] .. frame_off[c + 1] and one displacement row fewer than frames, so its first row
-// among all rows is frame_off[c] - c.
-#define P2S_JITTER_KPTS 26
-struct P2sJitterArgs {
-    const double *series;        // [frames][26][3] (x, y, confidence)
-    const int64_t *frame_off;    // [C + 1]
-    const int64_t *tile_base;    // [C + 1] first 256-row tile of every camera
-    double *disp;                // per camera [26][rows]: column-major, for the order statistics
-    double *area;                // [frames] box area, NaN with fewer than 2 valid keypoints
-    uint8_t *edge;               // [frames] 1: the box comes within 10 px of the image border
-    const double *stats;         // [C][27][2] the two middle values of the 26 displacement columns and the area column
-    const int64_t *stat_counts;  // [C][27] their non-NaN counts
-    double *medians, *thresholds;   // [C][26]
-    double *med_area;            // [C]
-    uint8_t *mask;               // [rows][26]
-    int32_t *counts;             // [C][26] events per keypoint (zeroed by the caller)
-    uint32_t *tile_count;        // [n_tiles]
-    long long *tile_off;         // [n_tiles] exclusive scan of tile_count
-    long long *n_events;
-    int32_t *events;             // [event_capacity][4] camera, frame, keypoint, pattern (0 A, 1 C, 2 D, 3 E)
-    int64_t event_capacity;
-    int64_t n_tiles, max_frames;
-    double multiplier, x_edge, y_edge;   // width - 10, height - 10
-    int32_t C;
-};
-hipError_t p2s_launch_jitter(const P2sJitterArgs &a, const P2sOrderArgs &o, hipStream_t s);
 
 #endif

@@ -17,9 +17,52 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "p2s_internal.h"
+#include <algorithm>
+#include <vector>
+
+#include "p2s_ctx.h"
 
 #pragma clang fp contract(off)
+
+// exact order statistics of fp64 columns, NaN skipped (np.nanmedian and its kin)
+struct P2sOrderArgs {
+    const double *data;
+    const int64_t *col_off;      // [n_cols] first element of every column, or NULL: col * n_rows
+    const int64_t *col_len;      // [n_cols] length of every column, or NULL: n_rows
+    const int64_t *ranks;        // [n_ranks] 0-based ranks among the non-NaN entries, negative = from the top; NULL: the
+                                 // two middle positions (m - 1) / 2 and m / 2 of every column (n_ranks is taken as 2)
+    double *out;                 // [n_cols][n_ranks]; NaN for a rank outside [0, m)
+    int64_t *counts;             // [n_cols] non-NaN entries m, or NULL
+    int64_t n_rows;
+    int32_t n_cols, n_ranks;
+};
+
+// 2D keypoint jitter analysis (Utilities/keypoint_jitter_analyze.py:143-325).  Cameras back to back:
+// camera c holds frames frame_off[c] .. frame_off[c + 1] and one displacement row fewer than frames, so its first row
+// among all rows is frame_off[c] - c.
+#define P2S_JITTER_KPTS 26
+struct P2sJitterArgs {
+    const double *series;        // [frames][26][3] (x, y, confidence)
+    const int64_t *frame_off;    // [C + 1]
+    const int64_t *tile_base;    // [C + 1] first 256-row tile of every camera
+    double *disp;                // per camera [26][rows]: column-major, for the order statistics
+    double *area;                // [frames] box area, NaN with fewer than 2 valid keypoints
+    uint8_t *edge;               // [frames] 1: the box comes within 10 px of the image border
+    const double *stats;         // [C][27][2] the two middle values of the 26 displacement columns and the area column
+    const int64_t *stat_counts;  // [C][27] their non-NaN counts
+    double *medians, *thresholds;   // [C][26]
+    double *med_area;            // [C]
+    uint8_t *mask;               // [rows][26]
+    int32_t *counts;             // [C][26] events per keypoint (zeroed by the caller)
+    uint32_t *tile_count;        // [n_tiles]
+    long long *tile_off;         // [n_tiles] exclusive scan of tile_count
+    long long *n_events;
+    int32_t *events;             // [event_capacity][4] camera, frame, keypoint, pattern (0 A, 1 C, 2 D, 3 E)
+    int64_t event_capacity;
+    int64_t n_tiles, max_frames;
+    double multiplier, x_edge, y_edge;   // width - 10, height - 10
+    int32_t C;
+};
 
 namespace {
 
@@ -394,13 +437,13 @@ __global__ void __launch_bounds__(1024) scan_tiles_kernel(const P2sJitterArgs a)
 
 }  // namespace
 
-hipError_t p2s_launch_order_stats(const P2sOrderArgs &a, hipStream_t s) {
+static hipError_t p2s_launch_order_stats(const P2sOrderArgs &a, hipStream_t s) {
     if (a.n_cols == 0) return hipSuccess;
     hipLaunchKernelGGL(order_stats_kernel, dim3((unsigned)a.n_cols), dim3(OS_THREADS), 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t p2s_launch_jitter(const P2sJitterArgs &a, const P2sOrderArgs &o, hipStream_t s) {
+static hipError_t p2s_launch_jitter(const P2sJitterArgs &a, const P2sOrderArgs &o, hipStream_t s) {
     const unsigned frame_tiles = (unsigned)((a.max_frames + FT - 1) / FT);
     hipLaunchKernelGGL(jitter_frames_kernel, dim3(frame_tiles, (unsigned)a.C), dim3(256), 0, s, a);
     hipError_t e = hipGetLastError();
@@ -417,3 +460,134 @@ hipError_t p2s_launch_jitter(const P2sJitterArgs &a, const P2sOrderArgs &o, hipS
     }
     return hipGetLastError();
 }
+
+// ---- C-ABI entry points (include/p2s.h) ----------------------------------------------------------------------------
+extern "C" {
+
+int p2s_column_order_stats_host(p2s_ctx *ctx, int64_t n_rows, int32_t n_cols, const double *data, int32_t n_ranks,
+                                const int64_t *ranks, double *out, int64_t *counts) {
+    if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
+    if (n_rows < 0 || n_rows >= ((int64_t)1 << 31) || n_cols < 0 || n_ranks < 0)
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "bad shape: %lld rows, %d columns, %d ranks", (long long)n_rows, n_cols, n_ranks);
+    if (n_cols == 0) return P2S_OK;
+    if ((n_rows > 0 && !data) || (n_ranks > 0 && (!ranks || !out))) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
+    const size_t data_b = (size_t)n_rows * n_cols * sizeof(double);
+    const size_t rank_b = (size_t)n_ranks * sizeof(int64_t), out_b = (size_t)n_cols * n_ranks * sizeof(double);
+    const size_t cnt_b = (size_t)n_cols * sizeof(int64_t);
+    HIP_TRY(hipSetDevice(ctx->device));
+    P2sOrderArgs a{};
+    a.n_rows = n_rows; a.n_cols = n_cols; a.n_ranks = n_ranks;
+    Stage st{ctx};
+    P2S_TRY(st.upload(a.data, data, data_b));
+    P2S_TRY(st.upload(a.ranks, ranks, rank_b));
+    P2S_TRY(st.alloc(a.counts, cnt_b + out_b));                   // one block, the 8-byte counts first: both parts stay aligned
+    a.out = (double *)(a.counts + n_cols);
+    HIP_TRY(p2s_launch_order_stats(a, ctx->stream));
+    P2S_TRY(st.down(out, a.out, out_b));
+    P2S_TRY(st.down(counts, a.counts, cnt_b));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return P2S_OK;
+}
+
+int p2s_jitter_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, const double *series, double multiplier,
+                    double image_width, double image_height, double *displacements, double *areas, double *medians,
+                    double *thresholds, double *median_area, uint8_t *mask, int32_t *counts, int64_t event_capacity,
+                    int32_t *events, int64_t *n_events) {
+    if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
+    if (n_cams < 1 || n_cams > 65535) return p2s_set_error(P2S_ERR_INVALID_ARG, "n_cams=%d outside [1, 65535]", n_cams);
+    if (!n_frames || !series) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
+    if (event_capacity < 0 || (event_capacity > 0 && !events)) return p2s_set_error(P2S_ERR_INVALID_ARG, "event_capacity=%lld without room", (long long)event_capacity);
+    constexpr int K = P2S_JITTER_KPTS, NS = K + 1;
+    const size_t C = (size_t)n_cams;
+    // host tables: frame_off [C+1], tile_base [C+1], col_off [C*27], col_len [C*27]
+    std::vector<int64_t> tab(2 * (C + 1) + 2 * C * NS);
+    int64_t *frame_off = tab.data(), *tile_base = frame_off + C + 1, *col_off = tile_base + C + 1, *col_len = col_off + C * NS;
+    int64_t max_frames = 0;
+    frame_off[0] = tile_base[0] = 0;
+    for (size_t c = 0; c < C; ++c) {
+        if (n_frames[c] < 1 || n_frames[c] >= ((int64_t)1 << 31))
+            return p2s_set_error(P2S_ERR_INVALID_ARG, "camera %zu has %lld frames; expected 1 .. 2^31 - 1", c, (long long)n_frames[c]);
+        frame_off[c + 1] = frame_off[c] + n_frames[c];
+        tile_base[c + 1] = tile_base[c] + (n_frames[c] - 1 + 255) / 256;
+        max_frames = std::max(max_frames, n_frames[c]);
+    }
+    const int64_t frames = frame_off[C], rows = frames - n_cams, n_tiles = tile_base[C];
+    if (frames > ((int64_t)1 << 33)) return p2s_set_error(P2S_ERR_INVALID_ARG, "%lld frames are too many", (long long)frames);
+    for (size_t c = 0; c < C; ++c) {                              // displacement columns, then the areas, in one allocation
+        const int64_t R = n_frames[c] - 1;
+        for (int k = 0; k < K; ++k) { col_off[c * NS + k] = K * (frame_off[c] - (int64_t)c) + k * R; col_len[c * NS + k] = R; }
+        col_off[c * NS + K] = K * rows + frame_off[c];
+        col_len[c * NS + K] = n_frames[c];
+    }
+    const size_t series_b = (size_t)frames * K * 3 * sizeof(double), disp_b = (size_t)rows * K * sizeof(double);
+    const size_t area_b = (size_t)frames * sizeof(double), tab_b = tab.size() * sizeof(int64_t);
+    // small device block after the tables: stats [C*27][2] f64, stat counts [C*27] i64, medians, thresholds [C*26] f64,
+    // median area [C] f64, n_events i64, counts [C*26] i32
+    const size_t o_stats = tab_b, o_scnt = o_stats + C * NS * 16, o_med = o_scnt + C * NS * 8, o_thr = o_med + C * K * 8;
+    const size_t o_marea = o_thr + C * K * 8, o_nev = o_marea + C * 8, o_cnt = o_nev + 8, small_b = o_cnt + C * K * 4;
+    HIP_TRY(hipSetDevice(ctx->device));
+    P2sJitterArgs a{};
+    Stage st{ctx};
+    char *sm;
+    P2S_TRY(st.upload(a.series, series, series_b));
+    P2S_TRY(st.alloc(a.disp, disp_b + area_b));
+    P2S_TRY(st.alloc(sm, small_b));
+    P2S_TRY(st.alloc(a.tile_off, (size_t)n_tiles * 16 + 16));
+    P2S_TRY(st.alloc(a.mask, (size_t)rows * K + 16));
+    P2S_TRY(st.alloc(a.edge, (size_t)frames));
+    P2S_TRY(st.alloc(a.events, (size_t)event_capacity * 16 + 16));
+    P2S_TRY(st.up(sm, tab.data(), tab_b));
+    a.frame_off = (const int64_t *)sm;
+    a.tile_base = a.frame_off + C + 1;
+    a.area = a.disp + (size_t)rows * K;
+    a.stats = (const double *)(sm + o_stats);
+    a.stat_counts = (const int64_t *)(sm + o_scnt);
+    a.medians = (double *)(sm + o_med);
+    a.thresholds = (double *)(sm + o_thr);
+    a.med_area = (double *)(sm + o_marea);
+    a.n_events = (long long *)(sm + o_nev);
+    a.counts = (int32_t *)(sm + o_cnt);
+    a.tile_count = (uint32_t *)((char *)a.tile_off + (size_t)n_tiles * 8 + 8);
+    a.event_capacity = event_capacity;
+    a.n_tiles = n_tiles; a.max_frames = max_frames;
+    a.multiplier = multiplier; a.x_edge = image_width - 10.0; a.y_edge = image_height - 10.0;
+    a.C = n_cams;
+    P2sOrderArgs o{};
+    o.data = a.disp;
+    o.col_off = a.tile_base + C + 1;
+    o.col_len = o.col_off + C * NS;
+    o.out = (double *)(sm + o_stats);
+    o.counts = (int64_t *)(sm + o_scnt);
+    o.n_cols = n_cams * NS; o.n_ranks = 2;                        // ranks NULL: the two middle positions
+    HIP_TRY(hipMemsetAsync(a.counts, 0, C * K * 4, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_stage[0], ctx->stream));
+    HIP_TRY(p2s_launch_jitter(a, o, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_stage[1], ctx->stream));
+    long long found = 0;
+    P2S_TRY(st.down(&found, a.n_events, 8));
+    P2S_TRY(st.down(displacements, a.disp, disp_b));
+    P2S_TRY(st.down(areas, a.area, area_b));
+    P2S_TRY(st.down(medians, a.medians, C * K * 8));
+    P2S_TRY(st.down(thresholds, a.thresholds, C * K * 8));
+    P2S_TRY(st.down(median_area, a.med_area, C * 8));
+    P2S_TRY(st.down(mask, a.mask, (size_t)rows * K));
+    P2S_TRY(st.down(counts, a.counts, C * K * 4));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                   // `tab` and `found` are host memory: alive until here
+    HIP_TRY(hipEventElapsedTime(&ctx->jitter_kernel_ms, ctx->ev_stage[0], ctx->ev_stage[1]));
+    const int64_t n_copy = std::min<int64_t>(found, event_capacity);
+    if (n_copy > 0) {
+        P2S_TRY(st.down(events, a.events, (size_t)n_copy * 16));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    if (n_events) *n_events = found;
+    return P2S_OK;
+}
+
+int p2s_jitter_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) {
+    if (!ctx || !elapsed_ms) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
+    if (ctx->jitter_kernel_ms < 0.0f) return p2s_set_error(P2S_ERR_INVALID_ARG, "p2s_jitter_host has not run on this context");
+    *elapsed_ms = ctx->jitter_kernel_ms;
+    return P2S_OK;
+}
+
+}  // extern "C"

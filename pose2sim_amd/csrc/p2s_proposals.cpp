@@ -14,8 +14,7 @@
 #include <vector>
 
 #include "p2s.h"
-
-int p2s_set_error(int code, const char *fmt, ...);   // p2s_api.hip
+#include "p2s_error.h"
 
 extern "C" int p2s_assoc_argmax_rows(int64_t n_frames, int32_t n_cams, int32_t n_max, const double *affinity,
                                      const int32_t *n_persons, int32_t n_threads, int32_t *rows) {

@@ -9,8 +9,24 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "p2s_internal.h"
+#include <cstring>
+#include <vector>
+
+#include "p2s_ctx.h"
 #include "p2s_tri_dev.h"      // project_distorted: the cv2.projectPoints restatement the triangulation kernels use
+
+// 3D markers onto the image planes (Utilities/reproj_from_trc_calib.py:446-475)
+struct P2sReprojArgs {
+    const double *Q;             // [n_frames][K][3], Z-up (X, Y, Z); NaN = missing
+    const double *P;             // plain mode: [C][Fp][12]
+    const P2sCam *cams;          // distorted mode: [C] (R, T, fx, fy, cx, cy, k read); NULL = plain mode
+    const double *sizes;         // [C][2] width, height
+    double *uv_raw;              // [C][n_frames][K][2] unrounded pixels, or NULL
+    double *uv;                  // [C][n_frames][K][2] rounded to one decimal, NaN outside the image
+    int64_t n_units;             // n_frames * K
+    int64_t Fp;                  // 1, or n_frames: one projection matrix per frame
+    int32_t K, C;
+};
 
 namespace {
 
@@ -62,7 +78,7 @@ __global__ void __launch_bounds__(256) p2s_reproject_kernel(const P2sReprojArgs 
 
 }  // namespace
 
-hipError_t p2s_launch_reproject(const P2sReprojArgs &a, hipStream_t s) {
+static hipError_t p2s_launch_reproject(const P2sReprojArgs &a, hipStream_t s) {
     if (a.n_units == 0 || a.C == 0) return hipSuccess;
     const int64_t blocks = (a.n_units + 255) / 256;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
@@ -75,3 +91,75 @@ hipError_t p2s_launch_reproject(const P2sReprojArgs &a, hipStream_t s) {
         hipLaunchKernelGGL((p2s_reproject_kernel<0>), grid, block, 0, s, a);
     return hipGetLastError();
 }
+
+// ---- C-ABI entry points (include/p2s.h) ----------------------------------------------------------------------------
+extern "C" {
+
+int p2s_reproject_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_markers, const double *Q, int32_t n_cams, int64_t n_frames_p,
+                       const double *P, const double *Kmat, const double *dist, const double *Rmat, const double *T,
+                       const double *sizes, int32_t flags, double *uv_raw, double *uv) {
+    if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
+    if (n_frames < 0 || n_markers < 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "bad shape: %lld frames, %d markers", (long long)n_frames, n_markers);
+    if (n_cams < 1 || n_cams > P2S_MAX_CAMS) return p2s_set_error(P2S_ERR_INVALID_ARG, "n_cams=%d outside [1, %d]", n_cams, P2S_MAX_CAMS);
+    if (flags & ~P2S_REPROJ_DISTORTED) return p2s_set_error(P2S_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
+    const bool distorted = (flags & P2S_REPROJ_DISTORTED) != 0;
+    if (distorted) {
+        if (n_frames_p != 1)
+            return p2s_set_error(P2S_ERR_INVALID_ARG, "distorted projection takes static cameras: n_frames_p=%lld, expected 1", (long long)n_frames_p);
+        if (!Kmat || !dist || !Rmat || !T) return p2s_set_error(P2S_ERR_INVALID_ARG, "distorted projection needs K, dist, R and T");
+    } else {
+        if (n_frames_p != 1 && n_frames_p != n_frames)
+            return p2s_set_error(P2S_ERR_INVALID_ARG, "n_frames_p=%lld is neither 1 nor n_frames=%lld", (long long)n_frames_p, (long long)n_frames);
+        if (!P) return p2s_set_error(P2S_ERR_INVALID_ARG, "null P");
+    }
+    if (!sizes) return p2s_set_error(P2S_ERR_INVALID_ARG, "null sizes");
+    if (!uv) return p2s_set_error(P2S_ERR_INVALID_ARG, "null uv");
+    const int64_t n_units = n_frames * (int64_t)n_markers;
+    ctx->reproj_kernel_ms = 0.0f;
+    if (n_units == 0) return P2S_OK;
+    if (!Q) return p2s_set_error(P2S_ERR_INVALID_ARG, "null Q");
+    if (n_units > ((int64_t)1 << 38) / n_cams) return p2s_set_error(P2S_ERR_INVALID_ARG, "%lld units x %d cameras is too large", (long long)n_units, n_cams);
+    const size_t q_b = (size_t)n_units * 3 * sizeof(double);
+    const size_t out_b = (size_t)n_units * n_cams * 2 * sizeof(double);
+    HIP_TRY(hipSetDevice(ctx->device));
+    P2sReprojArgs a{};
+    a.n_units = n_units; a.Fp = n_frames_p; a.K = n_markers; a.C = n_cams;
+    Stage st{ctx};
+    std::vector<P2sCam> cams;
+    if (distorted) {
+        cams.resize((size_t)n_cams);
+        std::memset(cams.data(), 0, sizeof(P2sCam) * (size_t)n_cams);
+        for (int c = 0; c < n_cams; ++c) {
+            P2sCam &cam = cams[(size_t)c];
+            const double *K = Kmat + 9 * c;
+            cam.fx = K[0]; cam.fy = K[4]; cam.cx = K[2]; cam.cy = K[5];     // the skew term is ignored, as in cv2.projectPoints
+            std::memcpy(cam.k, dist + 5 * c, sizeof cam.k);
+            std::memcpy(cam.R, Rmat + 9 * c, sizeof cam.R);
+            std::memcpy(cam.T, T + 3 * c, sizeof cam.T);
+        }
+        P2S_TRY(st.upload(a.cams, cams.data(), sizeof(P2sCam) * (size_t)n_cams));
+    } else {
+        P2S_TRY(st.upload(a.P, P, (size_t)n_cams * n_frames_p * 12 * sizeof(double)));
+    }
+    P2S_TRY(st.upload(a.sizes, sizes, (size_t)n_cams * 2 * sizeof(double)));
+    P2S_TRY(st.upload(a.Q, Q, q_b));
+    P2S_TRY(st.alloc(a.uv, out_b));
+    if (uv_raw) P2S_TRY(st.alloc(a.uv_raw, out_b));
+    HIP_TRY(hipEventRecord(ctx->ev_stage[0], ctx->stream));
+    HIP_TRY(p2s_launch_reproject(a, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_stage[1], ctx->stream));
+    P2S_TRY(st.down(uv, a.uv, out_b));
+    P2S_TRY(st.down(uv_raw, a.uv_raw, out_b));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));          // `cams` is pageable host memory: alive until here
+    HIP_TRY(hipEventElapsedTime(&ctx->reproj_kernel_ms, ctx->ev_stage[0], ctx->ev_stage[1]));
+    return P2S_OK;
+}
+
+int p2s_reproject_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) {
+    if (!ctx || !elapsed_ms) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
+    if (ctx->reproj_kernel_ms < 0.0f) return p2s_set_error(P2S_ERR_INVALID_ARG, "p2s_reproject_host has not run on this context");
+    *elapsed_ms = ctx->reproj_kernel_ms;
+    return P2S_OK;
+}
+
+}  // extern "C"

@@ -23,8 +23,7 @@
 #include <unistd.h>
 
 #include "p2s.h"
-
-int p2s_set_error(int code, const char *fmt, ...);                       // p2s_api.hip
+#include "p2s_error.h"
 extern "C" int p2s_format_float_repr(double value, char *out, int32_t capacity);   // p2s_trc.cpp
 
 namespace {

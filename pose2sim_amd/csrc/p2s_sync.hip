@@ -26,8 +26,35 @@
 #include <stdint.h>
 #include <math.h>
 
-#include "p2s_internal.h"
+#include <vector>
+
+#include "p2s_ctx.h"
 #include "p2s_iir.h"
+
+// synchronization speeds and their time-lagged Pearson correlation (synchronization.py:1271-1343, 1541-1575)
+struct P2sSyncArgs {
+    const double *coords;        // [total_rows][n_cols]: the cameras' masked (x, y) columns back to back
+    double *filled;              // [total_rows][n_cols]: interpolated, filled and filtered columns
+    double *work;                // [total_rows + 2 padlen n_cams][n_cols]: forward passes (camera c from row row0[c] + 2 padlen c)
+    double *speed;               // [total_rows]: sum of |vertical speeds|, then filtered in place
+    double *speed_work;          // [total_rows + 2 padlen n_cams]
+    const int64_t *row0;         // [n_cams + 1] first row of each camera
+    int64_t total_rows;
+    int32_t n_cams, n_cols, n_order, padlen;   // n_order = len(b) - 1; padlen = 3 len(b) (scipy's filtfilt)
+    int32_t filter_above;        // a camera is filtered when it has more frames than this (3 n_order, :1567)
+    double b[P2S_MAX_FILTER_ORDER + 1], a[P2S_MAX_FILTER_ORDER + 1], zi[P2S_MAX_FILTER_ORDER];
+};
+
+struct P2sPearsonArgs {
+    const double *ref;           // [n_ref]
+    const double *sig;           // the compared signals back to back
+    const int64_t *sig0;         // [n_sig + 1] offsets into sig
+    double *r;                   // [n_sig][n_lags]: r of lag lag_lo + t
+    int64_t *argmax;             // [n_sig]
+    double *max_corr;            // [n_sig]
+    int64_t n_ref, lag_lo, n_lags;
+    int32_t n_sig;
+};
 
 namespace {
 
@@ -252,7 +279,7 @@ __global__ void __launch_bounds__(256) p2s_pearson_argmax_kernel(const P2sPearso
 
 }  // namespace
 
-hipError_t p2s_launch_sync_speeds(const P2sSyncArgs &a, hipStream_t s) {
+static hipError_t p2s_launch_sync_speeds(const P2sSyncArgs &a, hipStream_t s) {
     const int64_t lanes = (int64_t)a.n_cams * a.n_cols, rows = a.total_rows;
     if (rows == 0) return hipSuccess;
     const unsigned grid_c = (unsigned)((lanes + 63) / 64), grid_r = (unsigned)((rows + 255) / 256);
@@ -272,10 +299,102 @@ hipError_t p2s_launch_sync_speeds(const P2sSyncArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t p2s_launch_pearson(const P2sPearsonArgs &a, hipStream_t s) {
+static hipError_t p2s_launch_pearson(const P2sPearsonArgs &a, hipStream_t s) {
     if (a.n_sig == 0 || a.n_lags == 0) return hipSuccess;
     const int64_t groups = (a.n_lags + kLagsPerWave - 1) / kLagsPerWave;
     hipLaunchKernelGGL(p2s_pearson_kernel, dim3((unsigned)((groups + 3) / 4), (unsigned)a.n_sig), dim3(256), 0, s, a);
     hipLaunchKernelGGL(p2s_pearson_argmax_kernel, dim3((unsigned)a.n_sig), dim3(256), 0, s, a);
     return hipGetLastError();
 }
+
+// ---- C-ABI entry points (include/p2s.h) ----------------------------------------------------------------------------
+extern "C" {
+
+int p2s_sync_speeds_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, int32_t n_cols, const double *coords,
+                         int32_t n_coef, const double *b, const double *a, const double *zi, double *speeds) {
+    if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
+    if (n_cams < 0 || n_cols < 0 || (n_cols & 1)) return p2s_set_error(P2S_ERR_INVALID_ARG, "bad shape: n_cams=%d n_cols=%d (x, y pairs)", n_cams, n_cols);
+    if (n_coef < 2 || n_coef > P2S_MAX_FILTER_ORDER + 1)
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "filter with %d coefficients: supported 2..%d", n_coef, P2S_MAX_FILTER_ORDER + 1);
+    if (n_cams == 0) return P2S_OK;
+    if (!n_frames || !b || !a || !zi || !speeds) return p2s_set_error(P2S_ERR_INVALID_ARG, "null pointer");
+    if (!(a[0] == 1.0)) return p2s_set_error(P2S_ERR_INVALID_ARG, "a[0] must be 1 (scipy.signal.butter normalises it)");
+    P2sSyncArgs f{};
+    f.n_cams = n_cams; f.n_cols = n_cols; f.n_order = n_coef - 1;
+    f.padlen = 3 * n_coef;                                   // scipy.signal.filtfilt's default
+    f.filter_above = 3 * (n_coef - 1);                       // synchronization.py:1539, 1567, 1584
+    for (int i = 0; i < n_coef; ++i) { f.b[i] = b[i]; f.a[i] = a[i]; }
+    for (int i = 0; i < n_coef - 1; ++i) f.zi[i] = zi[i];
+    std::vector<int64_t> row0((size_t)n_cams + 1, 0);
+    for (int c = 0; c < n_cams; ++c) {
+        const int64_t L = n_frames[c];
+        if (L < 2 || L > ((int64_t)1 << 31)) return p2s_set_error(P2S_ERR_INVALID_ARG, "camera %d: %lld frames (2 .. 2^31 supported)", c, (long long)L);
+        if (L > f.filter_above && L <= f.padlen)
+            return p2s_set_error(P2S_ERR_SYNC_PADLEN, "The length of the input vector x must be greater than padlen, which is %d.", f.padlen);
+        row0[(size_t)c + 1] = row0[(size_t)c] + L;
+    }
+    const int64_t rows = row0[(size_t)n_cams];
+    if (n_cols > 0 && !coords) return p2s_set_error(P2S_ERR_INVALID_ARG, "null coords");
+    f.total_rows = rows;
+    const int64_t wrows = rows + (int64_t)2 * f.padlen * n_cams;
+    const size_t cbytes = (size_t)rows * n_cols * sizeof(double), wbytes = (size_t)wrows * n_cols * sizeof(double);
+    // one block: speed [rows], speed_work [wrows], row0 [n_cams + 1]
+    const size_t sw_off = (size_t)rows * sizeof(double), r0_off = sw_off + (size_t)wrows * sizeof(double);
+    const size_t r0_b = row0.size() * sizeof(int64_t);
+    HIP_TRY(hipSetDevice(ctx->device));
+    Stage st{ctx};
+    char *aux;
+    P2S_TRY(st.alloc(f.coords, cbytes + 16));
+    P2S_TRY(st.up(f.coords, coords, cbytes));
+    P2S_TRY(st.alloc(f.filled, cbytes + 16));
+    P2S_TRY(st.alloc(f.work, wbytes + 16));
+    P2S_TRY(st.alloc(aux, r0_off + r0_b));
+    f.speed = (double *)aux; f.speed_work = (double *)(aux + sw_off); f.row0 = (const int64_t *)(aux + r0_off);
+    P2S_TRY(st.up(f.row0, row0.data(), r0_b));
+    HIP_TRY(p2s_launch_sync_speeds(f, ctx->stream));
+    P2S_TRY(st.down(speeds, f.speed, (size_t)rows * sizeof(double)));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return P2S_OK;
+}
+
+int p2s_lagged_pearson_host(p2s_ctx *ctx, const double *ref, int64_t n_ref, int32_t n_sig, const double *sig,
+                            const int64_t *sig_len, int64_t lag_lo, int64_t lag_hi, double *r, int64_t *argmax,
+                            double *max_corr) {
+    if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
+    if (n_ref < 0 || n_sig < 0 || n_ref > ((int64_t)1 << 31)) return p2s_set_error(P2S_ERR_INVALID_ARG, "bad shape: n_ref=%lld n_sig=%d", (long long)n_ref, n_sig);
+    if (lag_hi <= lag_lo || lag_hi - lag_lo > ((int64_t)1 << 31) || lag_lo < -((int64_t)1 << 40) || lag_hi > ((int64_t)1 << 40))
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "empty or too large lag range [%lld, %lld)", (long long)lag_lo, (long long)lag_hi);
+    if (n_sig == 0) return P2S_OK;
+    if (!sig_len || !r || !argmax || !max_corr || (n_ref > 0 && !ref)) return p2s_set_error(P2S_ERR_INVALID_ARG, "null pointer");
+    std::vector<int64_t> sig0((size_t)n_sig + 1, 0);
+    for (int i = 0; i < n_sig; ++i) {
+        if (sig_len[i] < 0 || sig_len[i] > ((int64_t)1 << 31)) return p2s_set_error(P2S_ERR_INVALID_ARG, "signal %d: bad length", i);
+        sig0[(size_t)i + 1] = sig0[(size_t)i] + sig_len[i];
+    }
+    const int64_t total = sig0[(size_t)n_sig];
+    if (total > 0 && !sig) return p2s_set_error(P2S_ERR_INVALID_ARG, "null signals");
+    P2sPearsonArgs p{};
+    p.n_ref = n_ref; p.lag_lo = lag_lo; p.n_lags = lag_hi - lag_lo; p.n_sig = n_sig;
+    // one input block: ref [n_ref + 1], sig [total + 1], sig0 [n_sig + 1]; one result block: argmax [n_sig], max_corr [n_sig]
+    const size_t sig_off = (size_t)(n_ref + 1) * sizeof(double), s0_off = sig_off + (size_t)(total + 1) * sizeof(double);
+    const size_t s0_b = sig0.size() * sizeof(int64_t), r_bytes = (size_t)n_sig * p.n_lags * sizeof(double);
+    HIP_TRY(hipSetDevice(ctx->device));
+    Stage st{ctx};
+    char *in;
+    P2S_TRY(st.alloc(in, s0_off + s0_b));
+    P2S_TRY(st.alloc(p.r, r_bytes));
+    P2S_TRY(st.alloc(p.argmax, (size_t)n_sig * 16));
+    p.ref = (const double *)in; p.sig = (const double *)(in + sig_off); p.sig0 = (const int64_t *)(in + s0_off);
+    p.max_corr = (double *)(p.argmax + n_sig);
+    P2S_TRY(st.up(p.ref, ref, (size_t)n_ref * sizeof(double)));
+    P2S_TRY(st.up(p.sig, sig, (size_t)total * sizeof(double)));
+    P2S_TRY(st.up(p.sig0, sig0.data(), s0_b));
+    HIP_TRY(p2s_launch_pearson(p, ctx->stream));
+    P2S_TRY(st.down(r, p.r, r_bytes));
+    P2S_TRY(st.down(argmax, p.argmax, (size_t)n_sig * 8));
+    P2S_TRY(st.down(max_corr, p.max_corr, (size_t)n_sig * 8));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return P2S_OK;
+}
+
+}  // extern "C"

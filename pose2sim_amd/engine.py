@@ -21,6 +21,31 @@ def _ptr(a):
     return C.c_void_p(int(a))
 
 
+def _optr(a):
+    """_ptr of an array, None for an empty one (the library takes NULL for "no data")."""
+    return _ptr(a) if a.size else None
+
+
+def _entry(lib, name):
+    """The entry point `name` of the loaded library; a library built before it existed is refused."""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise NotImplementedError(f'{_lib.LIB_PATH} has no {name}: rebuild it')
+    return fn
+
+
+def _cal_arrays(cal, n):
+    """K [n][9], dist [n][5] (k1, k2, p1, p2[, k3]), R [n][9], T [n][3] of a calibration dict, contiguous float64."""
+    d = np.zeros((n, 5))
+    for c in range(n):
+        dc = np.asarray(cal['dist'][c], dtype=np.float64).ravel()
+        if len(dc) > 5 and np.any(dc[5:] != 0):
+            raise P2sError('only k1,k2,p1,p2[,k3] distortion terms are supported')
+        d[c, :min(5, len(dc))] = dc[:5]
+    K, R, T = (np.ascontiguousarray(np.asarray(cal[k], dtype=np.float64).reshape(n, w)) for k, w in (('K', 9), ('R_mat', 9), ('T', 3)))
+    return K, d, R, T
+
+
 def as_packed(xyl):
     """Pick the narrowest exact dtype for an observation tensor: float32 when every value is
     float32-representable (RTMLib output is, poseEstimation.py:259), else float64, so that the
@@ -43,8 +68,7 @@ def write_openpose_files(cam_dirs, name_root, uv, marker_index=None, n_threads=0
     -> number of files written."""
     import os
     lib = _lib.load()
-    if not hasattr(lib, 'p2s_write_openpose_files'):
-        raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_write_openpose_files: rebuild it')
+    fn = _entry(lib, 'p2s_write_openpose_files')
     uv = np.ascontiguousarray(uv, dtype=np.float64)
     if uv.ndim != 4 or uv.shape[3] != 2 or uv.shape[0] != len(cam_dirs):
         raise P2sError(f'uv has shape {uv.shape}; expected [{len(cam_dirs)}][F][K][2]')
@@ -54,9 +78,8 @@ def write_openpose_files(cam_dirs, name_root, uv, marker_index=None, n_threads=0
     offsets = np.zeros(Cn + 1, dtype=np.int64)
     np.cumsum([len(n) for n in names], out=offsets[1:])
     done = C.c_int64(0)
-    _lib.check(lib.p2s_write_openpose_files(b''.join(names), _ptr(offsets), os.fsencode(name_root), Cn, F, K, len(idx),
-                                            _ptr(idx) if idx.size else None, _ptr(uv) if uv.size else None, int(n_threads),
-                                            C.byref(done)))
+    _lib.check(fn(b''.join(names), _ptr(offsets), os.fsencode(name_root), Cn, F, K, len(idx), _optr(idx), _optr(uv),
+                  int(n_threads), C.byref(done)))
     return done.value
 
 
@@ -89,15 +112,7 @@ class Engine:
         args = [None] * 5
         keep = [P]
         if cal is not None:
-            K = np.ascontiguousarray(np.asarray(cal['K'], dtype=np.float64).reshape(n, 9))
-            d = np.zeros((n, 5))
-            for c in range(n):
-                dc = np.asarray(cal['dist'][c], dtype=np.float64).ravel()
-                if len(dc) > 5 and np.any(dc[5:] != 0):
-                    raise P2sError('only k1,k2,p1,p2[,k3] distortion terms are supported')
-                d[c, :min(5, len(dc))] = dc[:5]
-            R = np.ascontiguousarray(np.asarray(cal['R_mat'], dtype=np.float64).reshape(n, 9))
-            T = np.ascontiguousarray(np.asarray(cal['T'], dtype=np.float64).reshape(n, 3))
+            K, d, R, T = _cal_arrays(cal, n)
             nk = np.ascontiguousarray(np.asarray(cal['optim_K'], dtype=np.float64).reshape(n, 9))
             keep += [K, d, R, T, nk]
             args = [_ptr(K), _ptr(d), _ptr(R), _ptr(T), _ptr(nk)]
@@ -226,8 +241,8 @@ class Engine:
         if len(a) != len(b) or len(zi) != len(b) - 1:
             raise P2sError('b, a and zi must have n, n and n - 1 coefficients')
         out = np.empty_like(data)
-        _lib.check(self._lib.p2s_butterworth_host(self._h, data.shape[0], data.shape[1], _ptr(data) if data.size else None,
-                                                  len(b), _ptr(b), _ptr(a), _ptr(zi), _ptr(out) if out.size else None))
+        _lib.check(self._lib.p2s_butterworth_host(self._h, data.shape[0], data.shape[1], _optr(data), len(b), _ptr(b), _ptr(a),
+                                                  _ptr(zi), _optr(out)))
         return out
 
     def filter_columns(self, kind, data, params):
@@ -239,8 +254,8 @@ class Engine:
             raise P2sError(f'data has shape {data.shape}; expected [n_frames][n_cols]')
         params = np.ascontiguousarray(params, dtype=np.float64).reshape(-1)
         out = np.empty_like(data)
-        _lib.check(self._lib.p2s_filter_columns_host(self._h, int(kind), data.shape[0], data.shape[1], _ptr(data) if data.size else None,
-                                                     _ptr(params) if params.size else None, params.size, _ptr(out) if out.size else None))
+        _lib.check(self._lib.p2s_filter_columns_host(self._h, int(kind), data.shape[0], data.shape[1], _optr(data), _optr(params),
+                                                     params.size, _optr(out)))
         return out
 
     _GCV_ERRORS = {_lib.P2S_ERR_GCV_SHORT_RUN: ValueError, _lib.P2S_ERR_GCV_ILL_POSED: ValueError,
@@ -253,8 +268,7 @@ class Engine:
         [n_frames][n_cols] the lambda of the fit at the first sample of every filtered run, NaN elsewhere.  Failures
         raise what the reference raises: ValueError (a run of 2 to 4 samples, an ill-posed problem, a search without a
         minimum, a negative lambda), numpy.linalg.LinAlgError (a singular system)."""
-        if not hasattr(self._lib, 'p2s_gcv_spline_host'):
-            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_gcv_spline_host: rebuild it')
+        fn = _entry(self._lib, 'p2s_gcv_spline_host')
         data = np.ascontiguousarray(data, dtype=np.float64)
         if data.ndim != 2:
             raise P2sError(f'data has shape {data.shape}; expected [n_frames][n_cols]')
@@ -262,9 +276,8 @@ class Engine:
         lam = 0.0 if auto else float((frame_rate / (2 * np.pi * float(cutoff))) ** 4)     # filtering.py:301
         out = np.empty_like(data)
         lam_out = np.full(data.shape, np.nan)
-        p = lambda x: _ptr(x) if x.size else None                           # noqa: E731
-        rc = self._lib.p2s_gcv_spline_host(self._h, data.shape[0], data.shape[1], p(data), 1 if auto else 0, lam,
-                                           float(smoothing_factor), p(out), p(lam_out))
+        rc = fn(self._h, data.shape[0], data.shape[1], _optr(data), 1 if auto else 0, lam, float(smoothing_factor), _optr(out),
+                _optr(lam_out))
         if rc in self._GCV_ERRORS:
             raise self._GCV_ERRORS[rc](self._lib.p2s_last_error().decode())
         if rc == _lib.P2S_ERR_INVALID_ARG and self._lib.p2s_last_error().decode() == 'Regularization parameter should be non-negative':
@@ -285,8 +298,8 @@ class Engine:
         bone_stats = np.full((nb, 3), np.nan)
         accel = np.full((K, max(F - 2, 0)), np.nan)
         missing = np.zeros(K, dtype=np.int64)
-        p = lambda x: _ptr(x) if x.size else None                           # noqa: E731
-        _lib.check(self._lib.p2s_trc_metrics_host(self._h, F, K, p(xyz), nb, p(bones), p(bone_len), p(bone_stats), p(accel), p(missing)))
+        _lib.check(self._lib.p2s_trc_metrics_host(self._h, F, K, _optr(xyz), nb, _optr(bones), _optr(bone_len), _optr(bone_stats),
+                                                  _optr(accel), _optr(missing)))
         return bone_len, bone_stats, accel, missing
 
     # -- a .trc back onto the image planes (Utilities/reproj_from_trc_calib.py:446-475) --------------------------------
@@ -296,8 +309,7 @@ class Engine:
         'dist' (k1, k2, p1, p2[, k3]), 'R_mat' and 'T' per camera: cv2.projectPoints with distortion, static cameras.
         sizes [C][2] (width, height).  -> uv [C][F][K][2] rounded to one decimal with NaN outside the image, as the
         reference stores it; with raw=True (uv, uv_raw), uv_raw being the pixels as computed."""
-        if not hasattr(self._lib, 'p2s_reproject_host'):
-            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_reproject_host: rebuild it')
+        fn = _entry(self._lib, 'p2s_reproject_host')
         Q = np.ascontiguousarray(Q, dtype=np.float64)
         if Q.ndim != 3 or Q.shape[2] != 3:
             raise P2sError(f'Q has shape {Q.shape}; expected [F][K][3]')
@@ -317,16 +329,7 @@ class Engine:
             flags = 0
         else:
             Cn, Fp = len(cal['K']), 1
-            Km = np.ascontiguousarray(np.asarray(cal['K'], dtype=np.float64).reshape(Cn, 9))
-            d = np.zeros((Cn, 5))
-            for c in range(Cn):
-                dc = np.asarray(cal['dist'][c], dtype=np.float64).ravel()
-                if len(dc) > 5 and np.any(dc[5:] != 0):
-                    raise P2sError('only k1,k2,p1,p2[,k3] distortion terms are supported')
-                d[c, :min(5, len(dc))] = dc[:5]
-            R = np.ascontiguousarray(np.asarray(cal['R_mat'], dtype=np.float64).reshape(Cn, 9))
-            T = np.ascontiguousarray(np.asarray(cal['T'], dtype=np.float64).reshape(Cn, 3))
-            keep = (Km, d, R, T)
+            keep = _cal_arrays(cal, Cn)
             args[1:] = [_ptr(x) for x in keep]
             flags = _lib.P2S_REPROJ_DISTORTED
         sizes = np.ascontiguousarray(sizes, dtype=np.float64)
@@ -334,16 +337,14 @@ class Engine:
             raise P2sError(f'sizes has shape {sizes.shape}; expected [{Cn}][2]')
         uv = np.empty((Cn, F, K, 2))
         uv_raw = np.empty((Cn, F, K, 2)) if raw else None
-        _lib.check(self._lib.p2s_reproject_host(self._h, F, K, _ptr(Q) if Q.size else None, Cn, Fp, *args, _ptr(sizes), flags,
-                                                _ptr(uv_raw) if raw else None, _ptr(uv)))
+        _lib.check(fn(self._h, F, K, _optr(Q), Cn, Fp, *args, _ptr(sizes), flags, _ptr(uv_raw) if raw else None, _ptr(uv)))
         return (uv, uv_raw) if raw else uv
 
     def reproject_kernel_ms(self):
         """Kernel time of the last reproject() call, from HIP events around it."""
-        if not hasattr(self._lib, 'p2s_reproject_kernel_ms'):
-            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_reproject_kernel_ms: rebuild it')
+        fn = _entry(self._lib, 'p2s_reproject_kernel_ms')
         ms = C.c_float(0)
-        _lib.check(self._lib.p2s_reproject_kernel_ms(self._h, C.byref(ms)))
+        _lib.check(fn(self._h, C.byref(ms)))
         return ms.value
 
     def write_openpose_files(self, cam_dirs, name_root, uv, marker_index=None, n_threads=0):
@@ -354,8 +355,7 @@ class Engine:
         """data [n_rows][n_cols] float64 (any strides; NaN entries are skipped), ranks: 0-based positions among each
         column's sorted non-NaN entries, negative = from the top.  -> (values [n_cols][n_ranks], NaN where the rank is
         outside the column's count; counts [n_cols] of non-NaN entries).  Exact: a radix select on the bit patterns."""
-        if not hasattr(self._lib, 'p2s_column_order_stats_host'):
-            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_column_order_stats_host: rebuild it')
+        fn = _entry(self._lib, 'p2s_column_order_stats_host')
         data = np.asarray(data, dtype=np.float64)
         if data.ndim != 2:
             raise P2sError(f'data has shape {data.shape}; expected [n_rows][n_cols]')
@@ -364,9 +364,7 @@ class Engine:
         n_cols, n_rows = cols.shape
         out = np.empty((n_cols, len(ranks)))
         counts = np.zeros(n_cols, dtype=np.int64)
-        _lib.check(self._lib.p2s_column_order_stats_host(self._h, n_rows, n_cols, _ptr(cols) if cols.size else None, len(ranks),
-                                                         _ptr(ranks) if ranks.size else None, _ptr(out) if out.size else None,
-                                                         _ptr(counts) if n_cols else None))
+        _lib.check(fn(self._h, n_rows, n_cols, _optr(cols), len(ranks), _optr(ranks), _optr(out), _optr(counts)))
         return out, counts
 
     def jitter(self, series, multiplier=5.0, image_size=(1920, 1080)):
@@ -375,8 +373,7 @@ class Engine:
         keep), 'bb_areas' [F], 'jitter_mask' [F-1][26] bool, 'medians', 'thresholds' [26], 'median_bb_area', 'counts' [26];
         and 'events' [n][4] int32 (camera, frame, keypoint, pattern 0 A / 1 C / 2 D / 3 E) for all cameras, in the
         reference's order."""
-        if not hasattr(self._lib, 'p2s_jitter_host'):
-            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_jitter_host: rebuild it')
+        fn = _entry(self._lib, 'p2s_jitter_host')
         series = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
         for s in series:
             if s.ndim != 3 or s.shape[1:] != (26, 3) or len(s) < 1:
@@ -391,10 +388,9 @@ class Engine:
         capacity = min(max(rows, 1) * 26, 1 << 18)
         while True:
             events, found = np.empty((capacity, 4), dtype=np.int32), C.c_int64(0)
-            _lib.check(self._lib.p2s_jitter_host(self._h, Cn, _ptr(n_frames), _ptr(flat), float(multiplier), float(image_size[0]),
-                                                 float(image_size[1]), _ptr(disp) if rows else None, _ptr(areas), _ptr(med), _ptr(thr),
-                                                 _ptr(med_area), _ptr(mask) if rows else None, _ptr(counts), capacity, _ptr(events),
-                                                 C.byref(found)))
+            _lib.check(fn(self._h, Cn, _ptr(n_frames), _ptr(flat), float(multiplier), float(image_size[0]), float(image_size[1]),
+                          _optr(disp), _ptr(areas), _ptr(med), _ptr(thr), _ptr(med_area), _optr(mask), _ptr(counts), capacity,
+                          _ptr(events), C.byref(found)))
             if found.value <= capacity:
                 break
             capacity = found.value                                # a second call with room for every event
@@ -411,10 +407,9 @@ class Engine:
 
     def jitter_kernel_ms(self):
         """Kernel time of the last jitter() call, from HIP events around its kernels."""
-        if not hasattr(self._lib, 'p2s_jitter_kernel_ms'):
-            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_jitter_kernel_ms: rebuild it')
+        fn = _entry(self._lib, 'p2s_jitter_kernel_ms')
         ms = C.c_float(0)
-        _lib.check(self._lib.p2s_jitter_kernel_ms(self._h, C.byref(ms)))
+        _lib.check(fn(self._h, C.byref(ms)))
         return ms.value
 
     # -- synchronization (synchronization.py:1271-1343, 1541-1585) -------------------------------------------------------
@@ -424,8 +419,7 @@ class Engine:
         with more than 3 (len(b) - 1) frames), sum of |vertical speed|, filter of that sum.  -> one speed array per
         camera.  A camera whose length lies between the reference's threshold and scipy's padlen raises scipy's
         ValueError."""
-        if not hasattr(self._lib, 'p2s_sync_speeds_host'):
-            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_sync_speeds_host: rebuild it')
+        fn = _entry(self._lib, 'p2s_sync_speeds_host')
         cols = [np.ascontiguousarray(c, dtype=np.float64) for c in coords]
         if any(c.ndim != 2 for c in cols) or len({c.shape[1] for c in cols}) > 1:
             raise P2sError('every camera needs an [n_frames][n_cols] array with the same n_cols')
@@ -437,9 +431,7 @@ class Engine:
         if len(a) != len(b) or len(zi) != len(b) - 1:
             raise P2sError('b, a and zi must have n, n and n - 1 coefficients')
         out = np.empty(int(lens.sum()), dtype=np.float64)
-        p = lambda x: _ptr(x) if x.size else None                           # noqa: E731
-        rc = self._lib.p2s_sync_speeds_host(self._h, len(cols), p(lens), n_cols, p(flat), len(b), _ptr(b), _ptr(a),
-                                            _ptr(zi), p(out))
+        rc = fn(self._h, len(cols), _optr(lens), n_cols, _optr(flat), len(b), _ptr(b), _ptr(a), _ptr(zi), _optr(out))
         if rc == _lib.P2S_ERR_SYNC_PADLEN:
             raise ValueError(self._lib.p2s_last_error().decode())
         _lib.check(rc)
@@ -448,8 +440,7 @@ class Engine:
     def lagged_pearson(self, ref, signals, lag_lo, lag_hi):
         """Series(ref).corr(Series(s).shift(lag)) for every signal s and lag in [lag_lo, lag_hi).
         -> (r [n_sig][n_lags], argmax [n_sig] as np.argmax of each r row, max_corr [n_sig] as np.nanmax)."""
-        if not hasattr(self._lib, 'p2s_lagged_pearson_host'):
-            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_lagged_pearson_host: rebuild it')
+        fn = _entry(self._lib, 'p2s_lagged_pearson_host')
         ref = np.ascontiguousarray(ref, dtype=np.float64).reshape(-1)
         sigs = [np.ascontiguousarray(s, dtype=np.float64).reshape(-1) for s in signals]
         lens = np.array([len(s) for s in sigs], dtype=np.int64)
@@ -458,9 +449,8 @@ class Engine:
         r = np.empty((len(sigs), max(n_lags, 0)), dtype=np.float64)
         arg = np.zeros(len(sigs), dtype=np.int64)
         mx = np.full(len(sigs), np.nan)
-        p = lambda x: _ptr(x) if x.size else None                           # noqa: E731
-        _lib.check(self._lib.p2s_lagged_pearson_host(self._h, p(ref), len(ref), len(sigs), p(flat), p(lens), int(lag_lo),
-                                                     int(lag_hi), p(r), p(arg), p(mx)))
+        _lib.check(fn(self._h, _optr(ref), len(ref), len(sigs), _optr(flat), _optr(lens), int(lag_lo), int(lag_hi), _optr(r),
+                      _optr(arg), _optr(mx)))
         return r, arg, mx
 
     # -- association -----------------------------------------------------------------------
@@ -486,9 +476,8 @@ class Engine:
         n_max = int(per_frame.max()) if F else 0
         n_max = max(2, (n_max + 1) & ~1)
         aff = np.zeros((F, n_max, n_max), dtype=np.float64)
-        _lib.check(self._lib.p2s_associate_host(self._h, F, kpts.shape[1], n_max, dtype, _ptr(n_persons),
-                                                _ptr(offsets), _ptr(kpts) if kpts.size else None, C.byref(params),
-                                                _ptr(aff)))
+        _lib.check(self._lib.p2s_associate_host(self._h, F, kpts.shape[1], n_max, dtype, _ptr(n_persons), _ptr(offsets),
+                                                _optr(kpts), C.byref(params), _ptr(aff)))
         return aff
 
     def associate_single(self, n_persons, tracked, reproj_thr, lik_thr, min_cams):
@@ -508,9 +497,8 @@ class Engine:
         err = np.full(F, np.inf)
         Q = np.full((F, 3), np.nan)
         prm = SingleParams(float(reproj_thr), float(lik_thr), int(min_cams), 0)
-        _lib.check(self._lib.p2s_associate_single_host(self._h, F, dtype, _ptr(n_persons), _ptr(offsets),
-                                                       _ptr(tracked) if tracked.size else None, C.byref(prm),
-                                                       _ptr(comb), _ptr(err), _ptr(Q)))
+        _lib.check(self._lib.p2s_associate_single_host(self._h, F, dtype, _ptr(n_persons), _ptr(offsets), _optr(tracked),
+                                                       C.byref(prm), _ptr(comb), _ptr(err), _ptr(Q)))
         return comb, err, Q
 
     def associate_single_device(self, F, dtype, d_n_persons, d_offsets, d_tracked, reproj_thr, lik_thr, min_cams,

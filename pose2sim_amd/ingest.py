@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .engine import _entry
 from ._lib import (P2S_F32, P2S_F64, P2S_JSON_NO_PEOPLE_LIST, P2S_JSON_PERSON_NO_LIST,  # noqa: F401
                    P2S_JSON_PERSON_NOT_NUMERIC, P2S_JSON_UNREADABLE)
 
@@ -103,13 +104,11 @@ class JsonBatch:
     def select_tracked_person(self, n_kpts=26, conf_threshold=0.1):
         """load_keypoints_series / _select_person (Utilities/keypoint_jitter_analyze.py:50-140) over the files in order:
         -> (series [n_files][n_kpts][3], status [n_files] P2S_TRACK_*, detail [n_files]); see p2s_json_select_tracked_person."""
-        if not hasattr(self._lib, 'p2s_json_select_tracked_person'):
-            raise NotImplementedError(f'{_lib.LIB_PATH} has no p2s_json_select_tracked_person: rebuild it')
+        fn = _entry(self._lib, 'p2s_json_select_tracked_person')
         out = np.empty((self.n_files, int(n_kpts), 3), dtype=np.float64)
         status = np.zeros(self.n_files, dtype=np.int32)
         detail = np.zeros(self.n_files, dtype=np.int32)
-        _lib.check(self._lib.p2s_json_select_tracked_person(self._h, int(n_kpts), float(conf_threshold), _ptr(out), _ptr(status),
-                                                            _ptr(detail)))
+        _lib.check(fn(self._h, int(n_kpts), float(conf_threshold), _ptr(out), _ptr(status), _ptr(detail)))
         return out, status, detail
 
 

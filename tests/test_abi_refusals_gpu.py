@@ -1,0 +1,109 @@
+"""Refusals of the downstream stages' C-ABI entry points, through the raw library with a live context: the return code
+and the exact p2s_last_error() text.  Every case returns before anything is launched or copied; the texts are the ones
+the library has always given (callers match on some of them), written out here rather than read from its source."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+INVALID, GCV_SHORT_RUN, SYNC_PADLEN = -1, -6, -10
+
+
+def P(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+f8 = lambda *shape: np.ones(shape)                                  # noqa: E731
+i8 = lambda *v: np.array(v, dtype=np.int64)                         # noqa: E731
+B, A, ZI = np.array([0.2, 0.4, 0.2]), np.array([1.0, -0.5, 0.3]), np.array([0.8, -0.1])
+A_BAD = np.array([2.0, -0.5, 0.3])
+NAN_DATA = np.array([[1.0, 2.0], [np.nan, 3.0], [4.0, 5.0]])
+SHORT_RUN = np.array([[1.0], [2.0], [3.0], [np.nan], [np.nan], [np.nan], [np.nan], [np.nan]])
+INF_RUN = np.array([[1.0], [2.0], [np.inf], [4.0], [5.0], [6.0]])
+OUT = np.empty(64)                                                  # room for any output of the cases below
+IOUT = np.empty(64, dtype=np.int64)
+
+# (entry point, arguments after the context, return code, message)
+CASES = [
+    ('p2s_butterworth_host', (4, 2, P(f8(4, 2)), 1, P(B), P(A), P(ZI), P(OUT)), INVALID, 'filter with 1 coefficients: supported 2..9'),
+    ('p2s_butterworth_host', (4, 2, P(f8(4, 2)), 3, P(B), P(A_BAD), P(ZI), P(OUT)), INVALID, 'a[0] must be 1 (scipy.signal.butter normalises it)'),
+    ('p2s_butterworth_host', (-1, 2, None, 3, P(B), P(A), P(ZI), None), INVALID, 'bad shape: n_frames=-1 n_cols=2'),
+    ('p2s_filter_columns_host', (99, 4, 2, P(f8(4, 2)), P(f8(1)), 1, P(OUT)), INVALID, 'unknown column filter 99'),
+    ('p2s_filter_columns_host', (1, 4, 2, P(f8(4, 2)), P(f8(2)), 2, P(OUT)), INVALID, 'Hampel filter: params = {n_sigma}'),
+    ('p2s_filter_columns_host', (3, 3, 2, P(NAN_DATA), P(np.array([3.0])), 1, P(OUT)), INVALID,
+     "median filter: the data hold NaN (scipy.signal.medfilt's answer for them is not defined)"),
+    ('p2s_gcv_spline_host', (8, 1, P(SHORT_RUN), 1, 0.0, 1.0, P(OUT), None), GCV_SHORT_RUN, '``x`` and ``y`` length must be at least 5'),
+    ('p2s_gcv_spline_host', (6, 1, P(INF_RUN), 1, 0.0, 1.0, P(OUT), None), INVALID, 'array must not contain infs or NaNs'),
+    ('p2s_gcv_spline_host', (-1, 2, None, 1, 0.0, 1.0, None, None), INVALID, 'bad shape: n_frames=-1 n_cols=2'),
+    ('p2s_trc_metrics_host', (2, -1, None, 0, None, None, None, None, None), INVALID, 'bad shape'),
+    ('p2s_trc_metrics_host', (2, 3, P(f8(2, 3, 3)), 1, P(np.array([0, 7], dtype=np.int32)), P(OUT), P(OUT), P(OUT), P(IOUT)), INVALID,
+     'bone 0 names marker 7 of 3'),
+    ('p2s_sync_speeds_host', (1, P(i8(40)), 3, P(f8(40, 3)), 3, P(B), P(A), P(ZI), P(OUT)), INVALID, 'bad shape: n_cams=1 n_cols=3 (x, y pairs)'),
+    ('p2s_sync_speeds_host', (1, P(i8(40)), 2, P(f8(40, 2)), 10, P(B), P(A), P(ZI), P(OUT)), INVALID, 'filter with 10 coefficients: supported 2..9'),
+    ('p2s_sync_speeds_host', (1, P(i8(8)), 2, P(f8(8, 2)), 3, P(B), P(A), P(ZI), P(OUT)), SYNC_PADLEN,
+     'The length of the input vector x must be greater than padlen, which is 9.'),
+    ('p2s_lagged_pearson_host', (P(f8(8)), 8, 1, P(f8(8)), P(i8(8)), 5, 5, P(OUT), P(IOUT), P(OUT)), INVALID, 'empty or too large lag range [5, 5)'),
+    ('p2s_lagged_pearson_host', (P(f8(8)), 8, 1, P(f8(8)), P(i8(-2)), -2, 3, P(OUT), P(IOUT), P(OUT)), INVALID, 'signal 0: bad length'),
+    ('p2s_reproject_host', (5, 2, P(f8(5, 2, 3)), 2, 3, P(f8(2, 3, 12)), None, None, None, None, P(f8(2, 2)), 0, None, P(OUT)), INVALID,
+     'n_frames_p=3 is neither 1 nor n_frames=5'),
+    ('p2s_reproject_host', (5, 2, P(f8(5, 2, 3)), 2, 1, P(f8(2, 1, 12)), None, None, None, None, P(f8(2, 2)), 4, None, P(OUT)), INVALID, 'unknown flags 0x4'),
+    ('p2s_reproject_host', (5, 2, P(f8(5, 2, 3)), 2, 5, None, P(f8(2, 9)), P(f8(2, 5)), P(f8(2, 9)), P(f8(2, 3)), P(f8(2, 2)), 1, None, P(OUT)), INVALID,
+     'distorted projection takes static cameras: n_frames_p=5, expected 1'),
+    ('p2s_column_order_stats_host', (4, 2, P(f8(2, 4)), -1, None, None, None), INVALID, 'bad shape: 4 rows, 2 columns, -1 ranks'),
+    ('p2s_column_order_stats_host', (4, 2, None, 1, P(i8(0)), P(OUT), None), INVALID, 'null argument'),
+    ('p2s_jitter_host', (1, P(i8(3)), P(f8(3, 26, 3)), 5.0, 1920.0, 1080.0) + (None,) * 7 + (8, None, None), INVALID, 'event_capacity=8 without room'),
+    ('p2s_jitter_host', (0, P(i8(3)), P(f8(3, 26, 3)), 5.0, 1920.0, 1080.0) + (None,) * 7 + (0, None, None), INVALID, 'n_cams=0 outside [1, 65535]'),
+    ('p2s_jitter_host', (1, P(i8(0)), P(f8(3, 26, 3)), 5.0, 1920.0, 1080.0) + (None,) * 7 + (0, None, None), INVALID,
+     'camera 0 has 0 frames; expected 1 .. 2^31 - 1'),
+]
+KEEP = [B, A, ZI, A_BAD, NAN_DATA, SHORT_RUN, INF_RUN, OUT, IOUT]    # the temporaries above are kept alive by ctypes' own references
+
+
+@pytest.fixture(scope='module')
+def lib():
+    from pose2sim_amd import _lib
+    return _lib.load()
+
+
+@pytest.fixture(scope='module')
+def ctx(lib):
+    h = C.c_void_p()
+    assert lib.p2s_create(0, C.byref(h)) == 0, lib.p2s_last_error()
+    yield h
+    lib.p2s_destroy(h)
+
+
+@pytest.mark.parametrize('name, args, code, text', CASES, ids=[f'{c[0]}-{i}' for i, c in enumerate(CASES)])
+def test_refusal_with_a_live_context(lib, ctx, name, args, code, text):
+    assert getattr(lib, name)(ctx, *args) == code
+    assert lib.p2s_last_error().decode() == text
+
+
+@pytest.mark.parametrize('name', sorted({c[0] for c in CASES}))
+def test_null_context_is_refused(lib, name):
+    args = next(c[1] for c in CASES if c[0] == name)
+    assert getattr(lib, name)(None, *args) == INVALID
+    assert lib.p2s_last_error().decode() == 'null context'
+
+
+def test_kernel_times_refuse_until_their_own_stage_has_run(lib):
+    """The two stages that time their kernels share one pair of events; each query still answers for its own stage."""
+    from pose2sim_amd.engine import Engine
+    ms = C.c_float(0)
+    for name in ('p2s_reproject_kernel_ms', 'p2s_jitter_kernel_ms'):
+        assert getattr(lib, name)(None, C.byref(ms)) == INVALID and lib.p2s_last_error().decode() == 'null argument'
+    eng = Engine(0)
+    assert lib.p2s_reproject_kernel_ms(eng._h, C.byref(ms)) == INVALID
+    assert lib.p2s_last_error().decode() == 'p2s_reproject_host has not run on this context'
+    assert lib.p2s_jitter_kernel_ms(eng._h, C.byref(ms)) == INVALID
+    assert lib.p2s_last_error().decode() == 'p2s_jitter_host has not run on this context'
+    P34 = np.array([[[1000.0, 0, 960, 0], [0, 1000.0, 540, 0], [0, 0, 1, 4.0]]])
+    eng.reproject(np.zeros((3, 2, 3)), P=P34, sizes=np.array([[1920.0, 1080.0]]))
+    assert eng.reproject_kernel_ms() >= 0.0
+    assert lib.p2s_jitter_kernel_ms(eng._h, C.byref(ms)) == INVALID                  # another stage's call does not count
+    assert lib.p2s_last_error().decode() == 'p2s_jitter_host has not run on this context'
+    eng.jitter([np.ones((4, 26, 3))])
+    assert eng.jitter_kernel_ms() >= 0.0 and eng.reproject_kernel_ms() >= 0.0
+    eng.close()
