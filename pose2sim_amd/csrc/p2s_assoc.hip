@@ -17,14 +17,29 @@
 // N = detections of the frame over all cameras (<= P2S_MAX_PERSONS_TOTAL).  Per frame the work is
 // ~10^7 fp64 flops on ~10 KB of input: compute/latency bound, LDS resident, no MFMA (the matrices
 // are 32 x 32 and every step is data dependent).
+//
+// The file ends with the C-ABI entry points of the stage, p2s_associate_device / _host.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <stdint.h>
 #include <math.h>
 
-#include "p2s.h"
-#include "p2s_internal.h"
+#include "p2s_ctx.h"
 #include "p2s_math.h"
+
+struct P2sAssocArgs {
+    const int32_t *n_persons;   // [F][C]
+    const int64_t *offsets;     // [F+1]
+    const void *kpts;           // [rows][Kj][3]
+    double *affinity;           // [F][Nmax][Nmax]
+    const P2sCam *cams;
+    int64_t n_frames;
+    int32_t C, Kj, Nmax, max_iter;
+    int32_t debug_mode;         // diagnostics only: 7 = per-frame phase timeline instead of the result (exp/assoc_trace.py)
+    int32_t form;               // P2S_ASSOC_FORM_* (p2s_set_tuning: tests run both kernels on the same frames)
+    unsigned long long *stats;  // sharded counters (frames, ADMM passes, Jacobi sweeps, fp64 operations) or NULL
+    double recon_thr, min_affinity, w_rank, tol, w_sparse;
+};
 
 namespace {
 
@@ -918,7 +933,7 @@ __global__ void __launch_bounds__(64, 3) p2s_assoc_kernel_s(const P2sAssocArgs a
     }
 }
 
-hipError_t p2s_launch_assoc(const P2sAssocArgs &a, int dtype, hipStream_t s) {
+static hipError_t p2s_launch_assoc(const P2sAssocArgs &a, int dtype, hipStream_t s) {
     if (a.Nmax <= 32 && a.form != P2S_ASSOC_FORM_GENERAL) {           // symmetric form, one wave per frame
         auto go_s = [&](auto kern, int R) -> hipError_t {
             const int LD = R + (R == 32 ? 2 : 4);                 // R + L / 2, as in the kernel
@@ -944,3 +959,85 @@ hipError_t p2s_launch_assoc(const P2sAssocArgs &a, int dtype, hipStream_t s) {
     if (dtype == P2S_F32) return two ? go(&p2s_assoc_kernel<float, 2>, 128) : go(&p2s_assoc_kernel<float, 1>, 64);
     return two ? go(&p2s_assoc_kernel<double, 2>, 128) : go(&p2s_assoc_kernel<double, 1>, 64);
 }
+
+// ---------------------------------------------------------------------------------------------
+// The C-ABI entry points of multi-person association (include/p2s.h).
+static int check_assoc(p2s_ctx *ctx, int64_t n_frames, int32_t Kj, int32_t n_max, int32_t dtype,
+                       const p2s_assoc_params *p) {
+    if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
+    if (ctx->n_cams <= 0 || !ctx->full_calib)
+        return p2s_set_error(P2S_ERR_NO_CALIB, "association needs K, R and T in p2s_set_calibration");
+    if (!p) return p2s_set_error(P2S_ERR_INVALID_ARG, "null params");
+    if (n_frames < 0 || n_frames > 0x7fffffffLL || Kj <= 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "bad shape");
+    if (n_max < 1 || n_max > P2S_MAX_PERSONS_TOTAL)
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "n_max=%d outside [1, %d]", n_max, P2S_MAX_PERSONS_TOTAL);
+    if (dtype != P2S_F32 && dtype != P2S_F64) return p2s_set_error(P2S_ERR_INVALID_ARG, "dtype must be P2S_F32 or P2S_F64");
+    if (!(p->reconstruction_error_threshold > 0)) return p2s_set_error(P2S_ERR_INVALID_ARG, "reconstruction_error_threshold must be > 0");
+    if (p->max_iter < 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "max_iter < 0");
+    return P2S_OK;
+}
+
+extern "C" {
+
+int p2s_associate_device(p2s_ctx *ctx, int64_t n_frames, int32_t n_kpts_json, int32_t n_max, int32_t dtype,
+                         const int32_t *d_n_persons, const int64_t *d_offsets, const void *d_kpts,
+                         const p2s_assoc_params *params, double *d_affinity) {
+    P2S_TRY(check_assoc(ctx, n_frames, n_kpts_json, n_max, dtype, params));
+    if (n_frames == 0) return P2S_OK;
+    if (!d_n_persons || !d_offsets || !d_kpts || !d_affinity) return p2s_set_error(P2S_ERR_INVALID_ARG, "null device pointer");
+    if (n_max & 1) return p2s_set_error(P2S_ERR_INVALID_ARG, "n_max must be even (pad the affinity stride)");
+    P2sAssocArgs a{};
+    a.n_persons = d_n_persons; a.offsets = d_offsets; a.kpts = d_kpts; a.affinity = d_affinity;
+    a.cams = ctx->d_cams;
+    a.n_frames = n_frames; a.C = ctx->n_cams; a.Kj = n_kpts_json; a.Nmax = n_max;
+    a.max_iter = params->max_iter;
+    a.debug_mode = ctx->debug_mode;
+    a.form = ctx->assoc_form;
+    a.stats = ctx->d_assoc_stats;
+    a.recon_thr = params->reconstruction_error_threshold; a.min_affinity = params->min_affinity;
+    a.w_rank = params->w_rank; a.tol = params->tol; a.w_sparse = params->w_sparse;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(p2s_launch_assoc(a, dtype, ctx->stream));
+    return P2S_OK;
+}
+
+int p2s_associate_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_kpts_json, int32_t n_max, int32_t dtype,
+                       const int32_t *n_persons, const int64_t *offsets, const void *kpts,
+                       const p2s_assoc_params *params, double *affinity) {
+    P2S_TRY(check_assoc(ctx, n_frames, n_kpts_json, n_max, dtype, params));
+    if (n_frames == 0) return P2S_OK;
+    if (!n_persons || !offsets || !affinity) return p2s_set_error(P2S_ERR_INVALID_ARG, "null host pointer");
+    const int C = ctx->n_cams;
+    // operand shapes are checked on the host before anything is launched
+    int64_t rows = 0;
+    for (int64_t f = 0; f < n_frames; ++f) {
+        if (offsets[f] != rows) return p2s_set_error(P2S_ERR_INVALID_ARG, "offsets[%lld] does not match n_persons", (long long)f);
+        int64_t nf = 0;
+        for (int c = 0; c < C; ++c) {
+            if (n_persons[f * C + c] < 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "negative person count");
+            nf += n_persons[f * C + c];
+        }
+        if (nf > n_max) return p2s_set_error(P2S_ERR_INVALID_ARG, "frame %lld has %lld detections > n_max=%d", (long long)f, (long long)nf, n_max);
+        rows += nf;
+    }
+    if (offsets[n_frames] != rows) return p2s_set_error(P2S_ERR_INVALID_ARG, "offsets[F] does not match n_persons");
+    if (rows > 0 && !kpts) return p2s_set_error(P2S_ERR_INVALID_ARG, "null kpts");
+    const size_t elem = dtype == P2S_F32 ? 4 : 8;
+    const size_t aff_bytes = (size_t)n_frames * n_max * n_max * sizeof(double);
+    HIP_TRY(hipSetDevice(ctx->device));
+    Stage st{ctx};
+    const void *d_kpts;
+    const int32_t *d_n_persons;
+    const int64_t *d_offsets;
+    double *d_affinity;
+    P2S_TRY(st.upload(d_kpts, kpts, (size_t)rows * n_kpts_json * 3 * elem));
+    P2S_TRY(st.upload(d_n_persons, n_persons, (size_t)n_frames * C * 4));
+    P2S_TRY(st.upload(d_offsets, offsets, (size_t)(n_frames + 1) * 8));
+    P2S_TRY(st.alloc(d_affinity, aff_bytes));
+    P2S_TRY(p2s_associate_device(ctx, n_frames, n_kpts_json, n_max, dtype, d_n_persons, d_offsets, d_kpts, params, d_affinity));
+    P2S_TRY(st.down(affinity, d_affinity, aff_bytes));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return P2S_OK;
+}
+
+}  // extern "C"

@@ -50,6 +50,7 @@ struct p2s_ctx {
     hipStream_t stream = nullptr;
     P2sCam *d_cams = nullptr;
     uint32_t *d_binom = nullptr;
+    uint32_t binom[33 * 33] = {};                    // the host's copy of d_binom: C(n, k) at [n * 33 + k], filled at creation
     int n_cams = 0;
     bool full_calib = false;     // K, dist, R, T, newK were provided
     hipEvent_t ev0 = nullptr, ev1 = nullptr;

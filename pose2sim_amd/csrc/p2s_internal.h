@@ -1,6 +1,7 @@
-// What more than one translation unit needs: the device-resident camera, the counter and work-list constants, and the
-// argument structs and launchers of the triangulation and association kernels, which p2s_api.hip drives.  The stages
-// downstream of the .trc keep their argument structs in their own .hip file, beside the kernels and the entry points.
+// What more than one translation unit needs: the device-resident camera, the counter and work-list constants, and what
+// the triangulation entry points (p2s_tri.hip) share with the kernels they drive in other files -- P2sTriArgs, the deep
+// rounds (p2s_tri_deep.hip) and the one-launch kernels (p2s_tri_fused.hip, p2s_tri_pool.hip).  Every other argument
+// struct stands in its stage's own .hip file, beside the kernels and the entry points.
 #ifndef P2S_INTERNAL_H
 #define P2S_INTERNAL_H
 
@@ -118,28 +119,6 @@ struct P2sDeepArgs {
 };
 hipError_t p2s_launch_deep_round(const struct P2sTriArgs &a, const P2sDeepArgs &d, int dtype, int grid_eval, int lds, hipStream_t s);
 
-struct P2sTriLaunch {
-    int grid0, threads0, lds0;   // level-0 (streaming) kernel
-    int grid1, threads1, lds1;   // search kernel
-    int force_tiled;             // diagnostics: use the LDS-tiled streaming kernel even when C <= 8
-};
-
-struct P2sAssocArgs {
-    const int32_t *n_persons;   // [F][C]
-    const int64_t *offsets;     // [F+1]
-    const void *kpts;           // [rows][Kj][3]
-    double *affinity;           // [F][Nmax][Nmax]
-    const P2sCam *cams;
-    int64_t n_frames;
-    int32_t C, Kj, Nmax, max_iter;
-    int32_t debug_mode;         // diagnostics only: 7 = per-frame phase timeline instead of the result (exp/assoc_trace.py)
-    int32_t form;               // P2S_ASSOC_FORM_* (p2s_set_tuning: tests run both kernels on the same frames)
-    unsigned long long *stats;  // sharded counters (frames, ADMM passes, Jacobi sweeps, fp64 operations) or NULL
-    double recon_thr, min_affinity, w_rank, tol, w_sparse;
-};
-
-hipError_t p2s_launch_tri(const P2sTriArgs &a, int dtype, const P2sTriLaunch &g, hipStream_t s, hipStream_t side,
-                          hipEvent_t k1_done);
 // p2s_tri_fused.hip: streaming pass + in-wave subset search in one launch (pinhole, no L/R swap, C <= 16); up to 8
 // cameras two tiles per wave, except for the last singles_pct % of every XCD's tiles
 bool p2s_tri_fused_supports(int C, int dtype, int undistort, int lr_swap);
@@ -147,21 +126,5 @@ hipError_t p2s_launch_tri_fused(const P2sTriArgs &a, int dtype, int singles_pct,
 // p2s_tri_pool.hip: persistent waves, failures pooled across tiles, fp32 screen + fp64 evaluation of the survivors
 bool p2s_tri_pool_supports(int C, int dtype, int undistort, int lr_swap);
 hipError_t p2s_launch_tri_pool(const P2sTriArgs &a, int dtype, int singles_pct, int tiles_per_wave, hipStream_t s);
-struct P2sSingleArgs {
-    const int32_t *n_persons;   // [F][C]
-    const int64_t *offsets;     // [F+1]
-    const void *tracked;        // [rows][3]
-    int32_t *comb;              // [F][C]
-    double *err;                // [F]
-    double *Q;                  // [F][3]
-    const P2sCam *cams;
-    const uint32_t *binom;
-    int64_t n_frames;
-    int32_t C, min_cams;
-    double thr, lik_thr;
-};
-hipError_t p2s_launch_single(const P2sSingleArgs &a, int dtype, hipStream_t s);
-
-hipError_t p2s_launch_assoc(const P2sAssocArgs &a, int dtype, hipStream_t s);
 
 #endif

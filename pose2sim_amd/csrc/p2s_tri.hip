@@ -20,14 +20,41 @@
 //            per level to minimise passes x rounds
 //
 // Everything is data-parallel fp64 VALU work on an HBM-streamed tensor: no MFMA (4x4 systems).
+//
+// The file ends with the C-ABI entry points of the stage: p2s_tri_geometry, p2s_triangulate_device / _host -- which
+// choose between the kernels here and the one-launch kernels of p2s_tri_pool.hip / p2s_tri_fused.hip and drive the
+// deep rounds of p2s_tri_deep.hip -- and p2s_associate_single_device / _host (p2s_single_kernel lives here).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <stdint.h>
 #include <math.h>
 
-#include "p2s_internal.h"
+#include <algorithm>
 
+#include "p2s_ctx.h"
 #include "p2s_tri_dev.h"
+
+// launch geometry of one chunk's kernel pair (tri_work_list fills it, p2s_launch_tri reads it)
+struct P2sTriLaunch {
+    int grid0, threads0, lds0;   // level-0 (streaming) kernel
+    int grid1, threads1, lds1;   // search kernel
+    int force_tiled;             // diagnostics: use the LDS-tiled streaming kernel even when C <= 8
+};
+
+// single-person association (p2s_single_kernel)
+struct P2sSingleArgs {
+    const int32_t *n_persons;   // [F][C]
+    const int64_t *offsets;     // [F+1]
+    const void *tracked;        // [rows][3]
+    int32_t *comb;              // [F][C]
+    double *err;                // [F]
+    double *Q;                  // [F][3]
+    const P2sCam *cams;
+    const uint32_t *binom;
+    int64_t n_frames;
+    int32_t C, min_cams;
+    double thr, lik_thr;
+};
 
 // ---------------------------------------------------------------------------------------------
 // Kernel 1 -- streaming pass.  LDS: [tile: FB*C*K*3 of T].
@@ -310,9 +337,7 @@ __global__ void __launch_bounds__(256, (CT <= 8 ? 4 : 3)) p2s_tri_level0_direct_
         sQ[wv][lane * 3 + 0] = fail ? d_nan() : Qb[0];
         sQ[wv][lane * 3 + 1] = fail ? d_nan() : Qb[1];
         sQ[wv][lane * 3 + 2] = fail ? d_nan() : Qb[2];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wsync();
         const int64_t wave_u0 = a.block0 * K + (lu - lane);        // first unit of this wave (global)
         const int64_t n_left = n_units - (lu - lane);              // units this wave owns
         double *Qw = a.Q + wave_u0 * 3;
@@ -336,9 +361,7 @@ __global__ void __launch_bounds__(256, (CT <= 8 ? 4 : 3)) p2s_tri_level0_direct_
         sE[wv][lane] = __float_as_uint(fail ? __builtin_nanf("") : (float)err_min);
         sM[wv][lane] = mask;
         sX[wv][lane] = (uint8_t)n_excl;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wsync();
         float *Ew = a.err + wave_u0;
         uint32_t *Mw = a.mask + wave_u0;
         uint8_t *Xw = a.n_excl + wave_u0;
@@ -454,9 +477,7 @@ __global__ void __launch_bounds__(256, 3) p2s_tri_search_kernel(const P2sTriArgs
             const int nw = n * (a.rec_bytes >> 2);
             for (int i = lane; i < nw; i += 64) dst[i] = src[i];
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wsync();
 
         if (trace) { __builtin_amdgcn_sched_barrier(0); t_fetch += __builtin_amdgcn_s_memtime() - t0; ++n_jobs; t0 = __builtin_amdgcn_s_memtime(); }
         const bool active = lane < n;
@@ -479,9 +500,7 @@ __global__ void __launch_bounds__(256, 3) p2s_tri_search_kernel(const P2sTriArgs
             reinterpret_cast<uint32_t *>(sN + 10)[0] = nanmask;
             reinterpret_cast<uint32_t *>(sN + 10)[1] = zeromask;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wsync();
 
         double err_min = kInf;
         double Qb[3] = {d_nan(), d_nan(), d_nan()};
@@ -569,9 +588,7 @@ __global__ void __launch_bounds__(256, 3) p2s_tri_search_kernel(const P2sTriArgs
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     if (lane < C) sPerm[pos] = (uint8_t)lane;
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    wsync();
                 }
 
                 for (uint32_t r0 = 0; r0 < nsub; r0 += G) {
@@ -816,9 +833,7 @@ __global__ void __launch_bounds__(64) p2s_single_kernel(const P2sSingleArgs a) {
         for (int i = lane; i < pc * 3; i += 64) tk[(c * PMAX) * 3 + i] = (double)src[row * 3 + i];
         row += pc;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wsync();
     uint32_t n_comb = 1;
     for (int c = 0; c < C; ++c) n_comb *= (uint32_t)max(1, min(a.n_persons[f * C + c], PMAX));
     const int missing = C - __popc(present);
@@ -951,7 +966,7 @@ __global__ void __launch_bounds__(64) p2s_single_kernel(const P2sSingleArgs a) {
     }
 }
 
-hipError_t p2s_launch_single(const P2sSingleArgs &a, int dtype, hipStream_t s) {
+static hipError_t p2s_launch_single(const P2sSingleArgs &a, int dtype, hipStream_t s) {
     const size_t lds = (((size_t)a.C * 16 * 24 + 64 * a.C + 15) / 16) * 16 + 33 * 33 * 4;
     if (dtype == 0)
         hipLaunchKernelGGL((p2s_single_kernel<float>), dim3((unsigned)a.n_frames), dim3(64), lds, s, a);
@@ -1010,7 +1025,392 @@ static hipError_t launch_t(const P2sTriArgs &a, const P2sTriLaunch &g, hipStream
     return a.lr_swap ? launch_both<T, false, true>(a, g, s, side, ev) : launch_both<T, false, false>(a, g, s, side, ev);
 }
 
-hipError_t p2s_launch_tri(const P2sTriArgs &a, int dtype, const P2sTriLaunch &g, hipStream_t s, hipStream_t side,
-                          hipEvent_t k1_done) {
+static hipError_t p2s_launch_tri(const P2sTriArgs &a, int dtype, const P2sTriLaunch &g, hipStream_t s, hipStream_t side,
+                                 hipEvent_t k1_done) {
     return dtype == 0 ? launch_t<float>(a, g, s, side, k1_done) : launch_t<double>(a, g, s, side, k1_done);
 }
+
+// ---------------------------------------------------------------------------------------------
+// The C-ABI entry points of triangulation and single-person association (include/p2s.h).  Operand shapes are
+// validated on the host before any kernel is launched.
+namespace {
+
+struct Geometry {
+    int FB, threads, lds_bytes;
+};
+
+int gcd_i(int a, int b) { return b ? gcd_i(b, a % b) : a; }
+
+// Tile geometry of the streaming kernel: FB consecutive (frame, person) blocks per workgroup.
+// The tile start must stay 16-byte aligned for the dwordx4 staging loads, the lanes of a workgroup
+// should be nearly all busy (FB*K close to a multiple of 64), and several workgroups should fit
+// the CU's 160 KB LDS.
+Geometry choose_geometry(int C, int K, int dtype) {
+    const int elem = dtype == P2S_F32 ? 4 : 8;
+    const long blk_bytes = (long)C * K * 3 * elem;
+    const int step = 16 / gcd_i(16, (int)(blk_bytes % 16 == 0 ? 16 : blk_bytes % 16));
+    Geometry best{};
+    double best_score = -1.0;
+    for (int FB = step; FB <= 4096; FB += step) {
+        const long tile = FB * blk_bytes;
+        const long lds = (tile + 15) / 16 * 16;
+        if (lds > 150 * 1024) break;
+        const long units = (long)FB * K;
+        const int threads = (int)std::min<long>(256, (units + 63) / 64 * 64);
+        const long passes = (units + threads - 1) / threads;
+        const double eff = (double)units / (double)(passes * threads);
+        const int wg_per_cu = (int)std::min<long>(8, (160 * 1024) / lds);
+        const int waves = std::min(32, wg_per_cu * threads / 64);
+        double score = eff * std::min(1.0, waves / 12.0);
+        if (lds > 64 * 1024) score *= 0.8;
+        if (passes > 1) score *= 0.9;
+        if (score > best_score + 1e-9) {
+            best_score = score;
+            best.FB = FB;
+            best.threads = threads;
+            best.lds_bytes = (int)lds;
+        }
+    }
+    if (best_score < 0) best.FB = 0;   // a single block does not fit: not supported
+    return best;
+}
+
+constexpr int64_t kChunkUnits = 1 << 22;   // units per (level-0, search) kernel pair: bounds the work-list scratch
+
+int check_tri(p2s_ctx *ctx, int64_t n_blocks, int32_t K, int32_t dtype, const p2s_tri_params *p,
+              const void *swap_idx) {
+    if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
+    if (ctx->n_cams <= 0) return p2s_set_error(P2S_ERR_NO_CALIB, "p2s_set_calibration has not been called");
+    if (!p) return p2s_set_error(P2S_ERR_INVALID_ARG, "null params");
+    if (n_blocks < 0 || K <= 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "bad shape: n_blocks=%lld K=%d", (long long)n_blocks, K);
+    if (dtype != P2S_F32 && dtype != P2S_F64) return p2s_set_error(P2S_ERR_INVALID_ARG, "dtype must be P2S_F32 or P2S_F64");
+    if (p->min_cameras < 1) return p2s_set_error(P2S_ERR_INVALID_ARG, "min_cameras must be >= 1 (got %d)", p->min_cameras);
+    if (!(p->reproj_error_threshold == p->reproj_error_threshold))
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "reproj_error_threshold is NaN");
+    if (p->undistort_points && !ctx->full_calib)
+        return p2s_set_error(P2S_ERR_NO_CALIB, "undistort_points needs K, dist, R, T and optim_K in p2s_set_calibration");
+    if (p->handle_lr_swap && !swap_idx) return p2s_set_error(P2S_ERR_INVALID_ARG, "handle_lr_swap needs swap_idx");
+    if (n_blocks * (int64_t)K >= (int64_t)1 << 40) return p2s_set_error(P2S_ERR_INVALID_ARG, "too many units");
+    return P2S_OK;
+}
+
+int check_single(p2s_ctx *ctx, int64_t n_frames, int32_t dtype, const p2s_single_params *p) {
+    if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
+    if (ctx->n_cams <= 0) return p2s_set_error(P2S_ERR_NO_CALIB, "p2s_set_calibration has not been called");
+    if (!p) return p2s_set_error(P2S_ERR_INVALID_ARG, "null params");
+    if (n_frames < 0 || n_frames > 0x7fffffffLL) return p2s_set_error(P2S_ERR_INVALID_ARG, "bad frame count");
+    if (dtype != P2S_F32 && dtype != P2S_F64) return p2s_set_error(P2S_ERR_INVALID_ARG, "dtype must be P2S_F32 or P2S_F64");
+    if (p->min_cameras < 1) return p2s_set_error(P2S_ERR_INVALID_ARG, "min_cameras must be >= 1");
+    return P2S_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int p2s_tri_geometry(int32_t n_cams, int32_t n_kpts, int32_t dtype, int32_t *blocks_per_tile, int32_t *threads,
+                     int32_t *lds_bytes) {
+    if (n_cams < 1 || n_cams > P2S_MAX_CAMS || n_kpts < 1 || (dtype != P2S_F32 && dtype != P2S_F64))
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "bad geometry query");
+    Geometry g = choose_geometry(n_cams, n_kpts, dtype);
+    if (g.FB == 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "one block of C=%d x K=%d does not fit in LDS", n_cams, n_kpts);
+    if (blocks_per_tile) *blocks_per_tile = g.FB;
+    if (threads) *threads = g.threads;
+    if (lds_bytes) *lds_bytes = g.lds_bytes;
+    return P2S_OK;
+}
+
+// The two paths of p2s_triangulate_device; the operands have been checked.
+// One launch per chunk: streaming pass + in-wave subset search (p2s_tri_fused.hip, p2s_tri_pool.hip).  A chunk keeps the
+// kernel's 32-bit byte offsets below 2^31 and starts on a multiple of 16 blocks (16-byte result stores).
+static int tri_one_launch(p2s_ctx *ctx, int64_t n_blocks, int32_t n_kpts, int32_t dtype, const void *d_xyl,
+                          const p2s_tri_params *params, double *d_Q, float *d_err, uint8_t *d_n_excl, uint32_t *d_excl_mask) {
+    const int C = ctx->n_cams;
+    const int elem = dtype == P2S_F32 ? 4 : 8;
+    P2sTriArgs a{};
+    a.xyl = d_xyl;
+    a.Q = d_Q; a.err = d_err; a.n_excl = d_n_excl; a.mask = d_excl_mask;
+    a.cams = ctx->d_cams;
+    a.sub_tab = ctx->d_sub_tab; a.sub_off = ctx->d_sub_off; a.binom = ctx->d_binom;
+    a.stats = ctx->d_stats;
+    a.K = n_kpts; a.C = C;
+    a.min_cams = params->min_cameras;
+    a.thr = params->reproj_error_threshold;
+    a.lik_thr = params->likelihood_threshold;
+    // the pooled kernel (persistent waves, fp32 screen) where it applies; P2S_TUNE_TRI_PATH picks the older forms
+    const bool pooled = (ctx->tri_path == P2S_TRI_PATH_AUTO || ctx->tri_path == P2S_TRI_PATH_POOLED) &&
+                        p2s_tri_pool_supports(C, dtype, params->undistort_points, params->handle_lr_swap);
+    a.screen = ctx->screen;
+    const int64_t blk_bytes = (int64_t)C * n_kpts * 3 * elem;
+    if (blk_bytes > ((int64_t)1 << 26)) return p2s_set_error(P2S_ERR_INVALID_ARG, "K=%d too large", n_kpts);
+    const int64_t chunk_blocks = std::max<int64_t>(16, (((int64_t)1 << 31) / blk_bytes) / 16 * 16);
+    HIP_TRY(hipSetDevice(ctx->device));
+    for (int64_t b0 = 0; b0 < n_blocks; b0 += chunk_blocks) {
+        a.block0 = b0;
+        a.n_blocks = std::min<int64_t>(chunk_blocks, n_blocks - b0);
+        if (pooled)
+            HIP_TRY(p2s_launch_tri_pool(a, dtype, ctx->pool_singles_pct, ctx->pool_tiles, ctx->stream));
+        else
+            HIP_TRY(p2s_launch_tri_fused(a, dtype, ctx->tri_path == P2S_TRI_PATH_ONE_TILE ? 100 : ctx->pool_singles_pct, ctx->stream));
+    }
+    return P2S_OK;
+}
+
+// Streaming pass, work list and search kernel per chunk of kChunkUnits units, deep levels in rounds over the whole GPU.
+static int tri_work_list(p2s_ctx *ctx, int64_t n_blocks, int32_t n_kpts, int32_t dtype, const void *d_xyl,
+                         const int32_t *d_swap_idx, const p2s_tri_params *params, double *d_Q, float *d_err,
+                         uint8_t *d_n_excl, uint32_t *d_excl_mask) {
+    const int C = ctx->n_cams;
+    const int elem = dtype == P2S_F32 ? 4 : 8;
+    Geometry g = choose_geometry(C, n_kpts, dtype);
+    if (g.FB == 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "one block of C=%d x K=%d does not fit in LDS", C, n_kpts);
+    const int rec_bytes = P2S_REC_HDR + (3 * C * elem * (params->handle_lr_swap ? 2 : 1) + 15) / 16 * 16;
+
+    // chunks of whole tiles, at most kChunkUnits units each
+    int64_t chunk_blocks = std::max<int64_t>(g.FB, (kChunkUnits / n_kpts) / g.FB * g.FB);
+    chunk_blocks = std::min<int64_t>(chunk_blocks, (n_blocks + g.FB - 1) / g.FB * g.FB);
+    const int64_t n_chunks = (n_blocks + chunk_blocks - 1) / chunk_blocks;
+    const int64_t chunk_units = chunk_blocks * n_kpts;
+    if (chunk_units > 0xffffffffLL / 2) return p2s_set_error(P2S_ERR_INVALID_ARG, "K=%d too large", n_kpts);
+
+    HIP_TRY(hipSetDevice(ctx->device));
+    // the work list: P2S_WL_SHARDS shards, workgroup b of the streaming kernel appends to shard b % SHARDS;
+    // two lists are used alternately by consecutive chunks; counters are zeroed on the stream first
+    const int64_t tiles_per_chunk = chunk_blocks / g.FB;
+    const int64_t shard_cap_tiled = (tiles_per_chunk + P2S_WL_SHARDS - 1) / P2S_WL_SHARDS * (int64_t)g.FB * n_kpts;
+    const int64_t direct_wgs = (chunk_units + 255) / 256;     // the direct kernel appends per 256-unit workgroup
+    const int64_t shard_cap_direct = (direct_wgs + P2S_WL_SHARDS - 1) / P2S_WL_SHARDS * 256;
+    const int64_t shard_cap = std::max(shard_cap_tiled, shard_cap_direct);
+    const size_t list_bytes = (size_t)P2S_WL_SHARDS * shard_cap * rec_bytes;
+    P2S_TRY(ctx->wl_rec.ensure(2 * list_bytes));
+    P2S_TRY(ctx->wl_count.ensure((size_t)n_chunks * 2 * P2S_WL_SHARDS * sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(ctx->wl_count.p, 0, (size_t)n_chunks * 2 * P2S_WL_SHARDS * sizeof(uint32_t), ctx->stream));
+
+    // search kernel geometry: LDS = [P][binom][waves x 64 records]
+    const int lds_binom_off = (C * 12 * 8 + 15) / 16 * 16;
+    const int lds_rec_off = (lds_binom_off + 33 * 33 * 4 + 15) / 16 * 16;
+    // records per search job: 40 (32..48 measure alike on cfg2) unless the records are large -- a wave's LDS region
+    // (job x (record + state)) is kept near 9 KB so that 3 waves per SIMD stay resident; with 32 cameras and the
+    // swapped copy a 40-record job took 35 KB and left less than one wave per SIMD (10 records there: 4.6 -> 2.0 s
+    // together with the two-pass swap evaluation; deep searches also balance better with small jobs)
+    int job = (int)std::max<int64_t>(8, std::min<int64_t>(40, (9 * 1024) / (int64_t)(rec_bytes + 96)));
+    if (ctx->job) job = ctx->job;                                                        // p2s_set_tuning: kernel experiments only
+    const int64_t fit = (40 * 1024) / (job * (int64_t)(rec_bytes + 96));
+    const int wpb = fit >= 4 ? 4 : fit >= 2 ? 2 : 1;   // waves per search workgroup
+    const int lds1 = lds_rec_off + wpb * job * (rec_bytes + 96);  // per wave: `job` records + `job` owner states
+    if (lds1 > 160 * 1024) return p2s_set_error(P2S_ERR_INVALID_ARG, "search records of C=%d do not fit in LDS", C);
+
+    P2sTriArgs a{};
+    a.xyl = d_xyl;
+    a.swap_idx = d_swap_idx;
+    a.Q = d_Q; a.err = d_err; a.n_excl = d_n_excl; a.mask = d_excl_mask;
+    a.cams = ctx->d_cams;
+    a.binom = ctx->d_binom;
+    a.stats = ctx->d_stats;
+    a.K = n_kpts; a.C = C; a.FB = g.FB;
+    a.rec_bytes = rec_bytes;
+    a.wl_capacity = (uint32_t)shard_cap;
+    a.lds_binom_off = lds_binom_off; a.lds_rec_off = lds_rec_off;
+    a.job = job;
+    a.max_subsets = ctx->max_subsets;
+    a.min_cams = params->min_cameras;
+    a.undistort = params->undistort_points ? 1 : 0;
+    a.lr_swap = params->handle_lr_swap ? 1 : 0;
+    a.thr = params->reproj_error_threshold;
+    a.lik_thr = params->likelihood_threshold;
+    a.debug_mode = ctx->debug_mode;                                   // 0 unless a -DP2S_DIAG build was told otherwise
+    a.prune = ctx->deep_prune;
+
+    // Deep levels: can a level of this camera count exceed the threshold at all?  Then units about to enter one are
+    // exported by the search kernel and finished by rounds of plan / eval / reduce over the whole GPU, chunk by chunk
+    // (the host reads a 4-byte count per round, so these calls synchronise the stream).
+    bool deep = false;
+    P2sDeepArgs dargs{};
+    constexpr uint32_t kDeepCapacity = 1u << 19, kDeepTickets = 1u << 20;
+    if (ctx->deep_min_subsets > 0)
+        for (int k = 1; k <= C - params->min_cameras; ++k) deep = deep || ctx->binom[C * 33 + k] > ctx->deep_min_subsets;
+    if (deep) {
+        if ((uint64_t)ctx->max_subsets > (uint64_t)kDeepTickets * P2S_DEEP_CHUNK)
+            return p2s_set_error(P2S_ERR_INVALID_ARG, "max subsets per level exceeds the deep-level ticket buffer");
+        const uint32_t obs_bytes = (uint32_t)(rec_bytes - P2S_REC_HDR);
+        const uint32_t entry_bytes = (uint32_t)((sizeof(P2sDeepEntry) + obs_bytes + 15) / 16 * 16);
+        P2S_TRY(ctx->deep_entries.ensure((size_t)kDeepCapacity * entry_bytes));
+        P2S_TRY(ctx->deep_ctl.ensure(64));
+        P2S_TRY(ctx->deep_sched.ensure((size_t)kDeepTickets * 2 * sizeof(uint32_t)));
+        P2S_TRY(ctx->deep_partials.ensure((size_t)kDeepTickets * sizeof(P2sDeepPartial)));
+        dargs.prune = ctx->deep_prune ? 1u : 0u;
+        dargs.entries = (unsigned char *)ctx->deep_entries.p;
+        dargs.ctl = (uint32_t *)ctx->deep_ctl.p;
+        dargs.sched_entry = (uint32_t *)ctx->deep_sched.p;
+        dargs.sched_chunk = dargs.sched_entry + kDeepTickets;
+        dargs.partials = (P2sDeepPartial *)ctx->deep_partials.p;
+        dargs.capacity = kDeepCapacity; dargs.max_tickets = kDeepTickets;
+        dargs.entry_bytes = entry_bytes; dargs.obs_bytes = obs_bytes;
+        a.deep_entries = dargs.entries; a.deep_ctl = dargs.ctl;
+        a.deep_capacity = kDeepCapacity; a.deep_entry_bytes = entry_bytes; a.deep_min_subsets = ctx->deep_min_subsets;
+    }
+
+    for (int64_t ch = 0; ch < n_chunks; ++ch) {
+        a.block0 = ch * chunk_blocks;
+        a.n_blocks = std::min<int64_t>(chunk_blocks, n_blocks - a.block0);
+        a.wl_count = (uint32_t *)ctx->wl_count.p + ch * 2 * P2S_WL_SHARDS;
+        a.wl_rec = (unsigned char *)ctx->wl_rec.p + (size_t)(ch & 1) * list_bytes;
+        P2sTriLaunch L{};
+        L.grid0 = (int)((a.n_blocks + g.FB - 1) / g.FB);
+        L.threads0 = g.threads;
+        L.lds0 = g.lds_bytes;
+        // persistent search grid: what stays resident at 3 waves per SIMD (256 CUs x 12 waves), no
+        // more than the chunk could ever need
+        const int64_t need_waves = (a.n_blocks * n_kpts + job - 1) / job;
+        const int64_t waves = std::max<int64_t>(wpb, std::min<int64_t>(3072, need_waves));
+        L.grid1 = (int)((waves + wpb - 1) / wpb);
+        L.threads1 = 64 * wpb;
+        L.lds1 = lds1;
+        L.force_tiled = ctx->force_tiled;                    // p2s_set_tuning: tests of the tiled kernel
+        const int slot = (int)(ch & 1);
+        const bool overlap = n_chunks > 1 && !ctx->no_overlap && !deep;
+        if (deep) HIP_TRY(hipMemsetAsync(dargs.ctl, 0, 64, ctx->stream));
+        hipStream_t side = overlap ? ctx->side_stream : ctx->stream;
+        if (overlap && ch >= 2) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_k2[slot], 0));   // list `slot` is free again
+        HIP_TRY(p2s_launch_tri(a, dtype, L, ctx->stream, side, ctx->ev_k1[slot]));
+        if (overlap) HIP_TRY(hipEventRecord(ctx->ev_k2[slot], side));
+        if (deep) {
+            uint32_t pending = 0;
+            HIP_TRY(hipMemcpyAsync(&pending, dargs.ctl + P2S_DEEP_N_ENTRIES, sizeof pending, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            const int deep_lds = lds_rec_off + 4 * (int)dargs.obs_bytes;
+            while (pending > 0) {
+                HIP_TRY(p2s_launch_deep_round(a, dargs, dtype, 256 * 3, deep_lds, ctx->stream));
+                HIP_TRY(hipMemcpyAsync(&pending, dargs.ctl + P2S_DEEP_PENDING, sizeof pending, hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(hipStreamSynchronize(ctx->stream));
+            }
+        }
+    }
+    if (n_chunks > 1 && !ctx->no_overlap && !deep) {   // join: the caller's stream sees every search finished
+        HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_k2[(n_chunks - 1) & 1], 0));
+        if (n_chunks > 1) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_k2[(n_chunks - 2) & 1], 0));
+    }
+    return P2S_OK;
+}
+
+int p2s_triangulate_device(p2s_ctx *ctx, int64_t n_blocks, int32_t n_kpts, int32_t dtype, const void *d_xyl,
+                           const int32_t *d_swap_idx, const p2s_tri_params *params, double *d_Q, float *d_err,
+                           uint8_t *d_n_excl, uint32_t *d_excl_mask) {
+    P2S_TRY(check_tri(ctx, n_blocks, n_kpts, dtype, params, d_swap_idx));
+    if (n_blocks == 0) return P2S_OK;
+    if (!d_xyl || !d_Q || !d_err || !d_n_excl || !d_excl_mask) return p2s_set_error(P2S_ERR_INVALID_ARG, "null device pointer");
+    if (((uintptr_t)d_xyl & 15) != 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "xyl must be 16-byte aligned");
+    const bool one_launch = ctx->tri_path != P2S_TRI_PATH_WORKLIST && !ctx->force_tiled &&
+                            p2s_tri_fused_supports(ctx->n_cams, dtype, params->undistort_points, params->handle_lr_swap);
+    if (one_launch) return tri_one_launch(ctx, n_blocks, n_kpts, dtype, d_xyl, params, d_Q, d_err, d_n_excl, d_excl_mask);
+    return tri_work_list(ctx, n_blocks, n_kpts, dtype, d_xyl, d_swap_idx, params, d_Q, d_err, d_n_excl, d_excl_mask);
+}
+
+int p2s_triangulate_host(p2s_ctx *ctx, int64_t n_blocks, int32_t n_kpts, int32_t dtype, const void *xyl,
+                         const int32_t *swap_idx, const p2s_tri_params *params, double *Q, float *err,
+                         uint8_t *n_excl, uint32_t *excl_mask) {
+    P2S_TRY(check_tri(ctx, n_blocks, n_kpts, dtype, params, swap_idx));
+    if (n_blocks == 0) return P2S_OK;
+    if (!xyl || !Q || !err || !n_excl || !excl_mask) return p2s_set_error(P2S_ERR_INVALID_ARG, "null host pointer");
+    const size_t elem = dtype == P2S_F32 ? 4 : 8;
+    const size_t n_units = (size_t)n_blocks * n_kpts;
+    HIP_TRY(hipSetDevice(ctx->device));
+    Stage st{ctx};
+    const void *d_xyl;
+    const int32_t *d_swap = nullptr;
+    double *d_Q;
+    float *d_err;
+    uint8_t *d_nexcl;
+    uint32_t *d_mask;
+    if (swap_idx) P2S_TRY(st.upload(d_swap, swap_idx, (size_t)n_kpts * 4));
+    P2S_TRY(st.upload(d_xyl, xyl, (size_t)n_blocks * ctx->n_cams * n_kpts * 3 * elem));
+    P2S_TRY(st.alloc(d_Q, n_units * 24));
+    P2S_TRY(st.alloc(d_err, n_units * 4));
+    P2S_TRY(st.alloc(d_nexcl, n_units));
+    P2S_TRY(st.alloc(d_mask, n_units * 4));
+    P2S_TRY(p2s_triangulate_device(ctx, n_blocks, n_kpts, dtype, d_xyl, d_swap, params, d_Q, d_err, d_nexcl, d_mask));
+    P2S_TRY(st.down(Q, d_Q, n_units * 24));
+    P2S_TRY(st.down(err, d_err, n_units * 4));
+    P2S_TRY(st.down(n_excl, d_nexcl, n_units));
+    P2S_TRY(st.down(excl_mask, d_mask, n_units * 4));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return P2S_OK;
+}
+
+int p2s_associate_single_device(p2s_ctx *ctx, int64_t n_frames, int32_t dtype, const int32_t *d_n_persons,
+                                const int64_t *d_offsets, const void *d_tracked, const p2s_single_params *params,
+                                int32_t *d_comb, double *d_err, double *d_Q) {
+    P2S_TRY(check_single(ctx, n_frames, dtype, params));
+    if (n_frames == 0) return P2S_OK;
+    if (!d_n_persons || !d_offsets || !d_tracked || !d_comb || !d_err || !d_Q)
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "null device pointer");
+    P2sSingleArgs a{};
+    a.n_persons = d_n_persons; a.offsets = d_offsets; a.tracked = d_tracked;
+    a.comb = d_comb; a.err = d_err; a.Q = d_Q;
+    a.cams = ctx->d_cams; a.binom = ctx->d_binom;
+    a.n_frames = n_frames; a.C = ctx->n_cams; a.min_cams = params->min_cameras;
+    a.thr = params->reproj_error_threshold; a.lik_thr = params->likelihood_threshold;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(p2s_launch_single(a, dtype, ctx->stream));
+    return P2S_OK;
+}
+
+int p2s_associate_single_host(p2s_ctx *ctx, int64_t n_frames, int32_t dtype, const int32_t *n_persons,
+                              const int64_t *offsets, const void *tracked, const p2s_single_params *params,
+                              int32_t *comb, double *err, double *Q) {
+    P2S_TRY(check_single(ctx, n_frames, dtype, params));
+    if (n_frames == 0) return P2S_OK;
+    if (!n_persons || !offsets || !comb || !err || !Q) return p2s_set_error(P2S_ERR_INVALID_ARG, "null host pointer");
+    const int C = ctx->n_cams;
+    int64_t rows = 0;
+    for (int64_t f = 0; f < n_frames; ++f) {       // operand shapes are checked before anything is launched
+        if (offsets[f] != rows) return p2s_set_error(P2S_ERR_INVALID_ARG, "offsets[%lld] does not match n_persons", (long long)f);
+        double prod = 1.0;
+        for (int c = 0; c < C; ++c) {
+            const int32_t n = n_persons[f * C + c];
+            if (n < 0 || n > P2S_MAX_PERSONS_PER_CAM)
+                return p2s_set_error(P2S_ERR_INVALID_ARG, "frame %lld camera %d: %d persons outside [0, %d]", (long long)f, c, n, P2S_MAX_PERSONS_PER_CAM);
+            rows += n;
+            prod *= n > 0 ? n : 1;
+        }
+        if (prod > (double)P2S_MAX_COMBINATIONS)
+            return p2s_set_error(P2S_ERR_INVALID_ARG, "frame %lld: %.0f person combinations exceed %d", (long long)f, prod, P2S_MAX_COMBINATIONS);
+        // worst case of the search (no combination ever gets under the threshold): every combination x every
+        // subset of up to (cameras with detections - min_cameras) cameras switched off.  The reference would
+        // run just as long; a frame that could keep one wave busy for minutes is refused instead.
+        int present = 0;
+        for (int c = 0; c < C; ++c) present += n_persons[f * C + c] > 0;
+        double subsets = 0.0, binom = 1.0;
+        for (int k = 0; k <= present - params->min_cameras; ++k) {
+            subsets += binom;
+            binom = binom * (present - k) / (k + 1);
+        }
+        if (prod * subsets > P2S_MAX_SINGLE_SEARCH)
+            return p2s_set_error(P2S_ERR_INVALID_ARG, "frame %lld: up to %.3g (combination, camera subset) evaluations exceed %.3g; raise "
+                        "min_cameras_for_triangulation or reduce the detections", (long long)f, prod * subsets, (double)P2S_MAX_SINGLE_SEARCH);
+    }
+    if (offsets[n_frames] != rows) return p2s_set_error(P2S_ERR_INVALID_ARG, "offsets[F] does not match n_persons");
+    if (rows > 0 && !tracked) return p2s_set_error(P2S_ERR_INVALID_ARG, "null tracked");
+    const size_t elem = dtype == P2S_F32 ? 4 : 8;
+    HIP_TRY(hipSetDevice(ctx->device));
+    Stage st{ctx};
+    const void *d_tracked;
+    const int32_t *d_n_persons;
+    const int64_t *d_offsets;
+    int32_t *d_comb;
+    double *d_err, *d_Q;
+    P2S_TRY(st.upload(d_tracked, tracked, (size_t)rows * 3 * elem));
+    P2S_TRY(st.upload(d_n_persons, n_persons, (size_t)n_frames * C * 4));
+    P2S_TRY(st.upload(d_offsets, offsets, (size_t)(n_frames + 1) * 8));
+    P2S_TRY(st.alloc(d_comb, (size_t)n_frames * C * 4));
+    P2S_TRY(st.alloc(d_err, (size_t)n_frames * 8));
+    P2S_TRY(st.alloc(d_Q, (size_t)n_frames * 24));
+    P2S_TRY(p2s_associate_single_device(ctx, n_frames, dtype, d_n_persons, d_offsets, d_tracked, params, d_comb, d_err, d_Q));
+    P2S_TRY(st.down(comb, d_comb, (size_t)n_frames * C * 4));
+    P2S_TRY(st.down(err, d_err, (size_t)n_frames * 8));
+    P2S_TRY(st.down(Q, d_Q, (size_t)n_frames * 24));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return P2S_OK;
+}
+
+}  // extern "C"

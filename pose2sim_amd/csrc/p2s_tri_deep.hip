@@ -29,14 +29,6 @@
 
 namespace {
 
-constexpr uint32_t kNone = 0xffffffffu;
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ P2sDeepEntry *entry_at(const P2sDeepArgs &d, uint32_t i) {
     return reinterpret_cast<P2sDeepEntry *>(d.entries + (size_t)i * d.entry_bytes);
 }
@@ -134,7 +126,7 @@ __global__ void __launch_bounds__(256, 3) p2s_deep_eval_kernel(const P2sTriArgs 
             uint32_t *dst = reinterpret_cast<uint32_t *>(sObs);
             for (int i = lane; i < (int)(d.obs_bytes >> 2); i += 64) dst[i] = src[i];
         }
-        wave_sync();
+        wsync();
         UnitObs<T> oobs{sObs, 3, a.lik_thr};
         UnitObs<T> oobs_sw = oobs;
         if (LRSWAP) oobs_sw.p = sObs + C * 3;
@@ -177,10 +169,10 @@ __global__ void __launch_bounds__(256, 3) p2s_deep_eval_kernel(const P2sTriArgs 
                 const double r2 = shfl_d(res, c2);
                 pos += (r2 > res || (r2 == res && c2 < lane)) ? 1 : 0;
             }
-            wave_sync();
+            wsync();
             if (lane < C) sPerm[pos] = (uint8_t)lane;
         }
-        wave_sync();
+        wsync();
         // no further level will replace this one's result: the unit's last level, or the next one is behind the valve
         double Nsw[10];
         uint32_t nan_sw = 0;
@@ -334,7 +326,7 @@ __global__ void __launch_bounds__(256, 3) p2s_deep_eval_kernel(const P2sTriArgs 
             p.e = be; p.q[0] = bq0; p.q[1] = bq1; p.q[2] = bq2; p.rank = brank; p.S = bS;
             p.se = se; p.sq[0] = sq0; p.sq[1] = sq1; p.sq[2] = sq2; p.srank = srank; p.sS = sS;
         }
-        wave_sync();                                        // the next ticket overwrites this wave's LDS region
+        wsync();                                            // the next ticket overwrites this wave's LDS region
     }
 }
 

@@ -1,5 +1,6 @@
 // p2s_tri_dev.h -- device-side building blocks shared by the triangulation kernels (p2s_tri.hip: streaming,
-// tiled and work-list search kernels; p2s_tri_fused.hip: the one-launch kernel with the in-wave subset search).
+// tiled and work-list search kernels; p2s_tri_deep.hip: the deep rounds; p2s_tri_fused.hip and p2s_tri_pool.hip: the
+// one-launch kernels with the in-wave subset search, whose wave-level helpers are the last section).
 // Everything here is static / inline: each translation unit gets its own copy.
 #ifndef P2S_TRI_DEV_H
 #define P2S_TRI_DEV_H
@@ -610,6 +611,59 @@ __device__ __forceinline__ double swap_error_pruned(cam_cptr cams, int C, const 
     if (!__any(alive)) return kInf;
     const double es = swap_error<T, UNDISTORT, 0>(cams, C, osw, kept, M, qs);
     return alive ? es : kInf;
+}
+
+// --------------------------------------------------------------------------------------------
+// Wave-level pieces: one wave works through LDS without a workgroup barrier.  wsync() is for every kernel that does;
+// the rest is what the two one-launch kernels (p2s_tri_fused.hip, p2s_tri_pool.hip) have in common.
+constexpr uint32_t kNone = 0xffffffffu;    // no candidate yet (rank), no slot
+
+// What the wave's lanes wrote to LDS before is visible to all of them after.
+__device__ __forceinline__ void wsync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The observations of a unit parked in an LDS slot: x, y, likelihood per camera (mean_error reads them).
+template <typename T>
+struct SlotObs {
+    const T *o;
+    double lik_thr;
+    __device__ __forceinline__ void raw(int c, double &x, double &y, double &wo) const {
+        x = (double)o[3 * c]; y = (double)o[3 * c + 1]; wo = 0.0;
+    }
+    __device__ __forceinline__ void rawT(int c, T &x, T &y, T &wo) const { x = o[3 * c]; y = o[3 * c + 1]; wo = o[3 * c + 2]; }
+};
+
+// Quirk Q1: a subset that removes cameras which do not count anyway (o_d: NaN or zero likelihood) duplicates another
+// one; only the lexicographically first padding -- the lowest such cameras -- can win the argmin.
+__device__ __forceinline__ bool first_padding(uint32_t S, uint32_t o_d) {
+    const uint32_t pad = S & o_d;
+    const uint32_t below = pad ? ((2u << (31 - __builtin_clz(pad))) - 1u) : 0u;
+    return (o_d & below) == pad;
+}
+
+// The host's side of the tile dealing (the kernels' side stands at the head of either kernel): workgroups go
+// round-robin over the 8 XCDs, every XCD gets a contiguous range of tiles; of those the last singles_pct % go out one
+// tile per workgroup, the rest before them in whole groups of tpw.  Fills a.pool_pairs / a.pool_singles (workgroups per
+// XCD of either kind) and returns the grid.
+inline unsigned deal_grid(P2sTriArgs &a, int singles_pct, int tpw) {
+    const int64_t n_units = a.n_blocks * a.K;
+    const int64_t n_tiles = (n_units + 63) / 64;
+    const int64_t per_xcd = (n_tiles + 7) / 8;
+    int64_t singles = per_xcd * singles_pct / 100;
+    singles += (per_xcd - singles) % tpw;
+    a.pool_singles = (uint32_t)singles;
+    a.pool_pairs = (uint32_t)((per_xcd - singles) / tpw);
+    return (unsigned)(8 * (a.pool_pairs + a.pool_singles));
+}
+
+// This lane's unit of a tile (index within the chunk); a lane beyond the last unit works on the tile's first one.
+__device__ __forceinline__ uint32_t unit_of(uint32_t tile, int lane, int64_t n_units, bool &active) {
+    const int64_t lu = ((int64_t)tile << 6) + lane;
+    active = lu < n_units;
+    return active ? (uint32_t)lu : (uint32_t)(tile << 6);
 }
 
 }  // namespace

@@ -29,7 +29,6 @@
 
 namespace {
 
-constexpr uint32_t kNone = 0xffffffffu;
 constexpr int kSlots = 32;                 // units a wave searches at a time (more: further rounds, observations re-read)
 
 template <typename T, int CT>
@@ -41,16 +40,8 @@ struct alignas(16) PSlot {
     T o[CT * 3];                           // x, y, likelihood per camera
 };
 
-template <typename T>
-struct SlotObs {
-    const T *o;
-    double lik_thr;
-    __device__ __forceinline__ void raw(int c, double &x, double &y, double &wo) const {
-        x = (double)o[3 * c]; y = (double)o[3 * c + 1]; wo = 0.0;
-    }
-    __device__ __forceinline__ void rawT(int c, T &x, T &y, T &wo) const { x = o[3 * c]; y = o[3 * c + 1]; wo = o[3 * c + 2]; }
-};
-
+// (p2s_tri_pool.hip's load_obs reads a camera beyond C at camera 0's address and zeroes it, without a branch; taken over
+// here that form moved the kernels compiled for a range of camera counts by up to 21 vector registers, so this one stays)
 template <typename T, int CT, bool EXACT>
 __device__ __forceinline__ void load_obs(const P2sTriArgs &a, int C, uint32_t b, uint32_t k, RegObs<T, CT> &obs) {
     const unsigned char *chunk = reinterpret_cast<const unsigned char *>(a.xyl) +
@@ -68,12 +59,6 @@ __device__ __forceinline__ void load_obs(const P2sTriArgs &a, int C, uint32_t b,
             obs.x[c] = obs.y[c] = obs.w[c] = (T)0;
         }
     }
-}
-
-__device__ __forceinline__ void wsync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 template <typename T, int CT, bool EXACT, int TPW>
@@ -119,11 +104,6 @@ __global__ void __launch_bounds__(64, 3) p2s_tri_fused_kernel(const P2sTriArgs a
 
     // ---- level 0 of every tile (triangulation.py:404-505 with nb_cams_off = 0) ----------------------------------------
     int n_hard = 0;                                                     // searching units so far (wave-uniform)
-    auto unit_of = [&](uint32_t tile, bool &active) -> uint32_t {
-        const int64_t lu = ((int64_t)tile << 6) + lane;
-        active = lu < n_units;
-        return active ? (uint32_t)lu : (uint32_t)(tile << 6);
-    };
     // Level 0 of one tile.  `prefetch` is called once the eigen-solve is through (the point of highest register
     // pressure): the first tile requests the second tile's observations there, so that they travel during its
     // reprojection pass instead of after it.
@@ -171,13 +151,13 @@ __global__ void __launch_bounds__(64, 3) p2s_tri_fused_kernel(const P2sTriArgs a
     RegObs<T, CT> obs0, obs1, obs2;
     obs0.lik_thr = a.lik_thr; obs1.lik_thr = a.lik_thr; obs2.lik_thr = a.lik_thr;
     bool act0, act1 = false, act2 = false;
-    const uint32_t u0 = unit_of(tile0, act0);
+    const uint32_t u0 = unit_of(tile0, lane, n_units, act0);
     load_obs<T, CT, EXACT>(a, C, u0 / (uint32_t)K, u0 % (uint32_t)K, obs0);
     const bool two = my_tiles > 1 && tile0 + tstride < n_tiles;
     const bool three = TPW > 2 && my_tiles > 2 && tile0 + 2 * tstride < n_tiles;
     level0(0, act0, obs0, [&](double dep) {
         if (two) {
-            uint32_t u1 = unit_of(tile0 + tstride, act1);
+            uint32_t u1 = unit_of(tile0 + tstride, lane, n_units, act1);
             asm volatile("" : "+v"(u1) : "v"(dep));                     // not before the eigen-solve
             load_obs<T, CT, EXACT>(a, C, u1 / (uint32_t)K, u1 % (uint32_t)K, obs1);
         }
@@ -185,7 +165,7 @@ __global__ void __launch_bounds__(64, 3) p2s_tri_fused_kernel(const P2sTriArgs a
     if (two) level0(1, act1, obs1, [&](double dep) {
         if constexpr (TPW > 2) {
             if (three) {
-                uint32_t u2 = unit_of(tile0 + 2 * tstride, act2);
+                uint32_t u2 = unit_of(tile0 + 2 * tstride, lane, n_units, act2);
                 asm volatile("" : "+v"(u2) : "v"(dep));
                 load_obs<T, CT, EXACT>(a, C, u2 / (uint32_t)K, u2 % (uint32_t)K, obs2);
             }
@@ -264,10 +244,7 @@ __global__ void __launch_bounds__(64, 3) p2s_tri_fused_kernel(const P2sTriArgs a
                             // level 1 is rank r <-> camera r (itertools.combinations order); only the deeper levels go to
                             // the table in global memory (a load per pass, and its latency)
                             S = (level == 1) ? (1u << r) : (uint32_t)a.sub_tab[sub0 + r];
-                            // quirk Q1 duplicates: only the lexicographically first padding can win the argmin
-                            const uint32_t pad = S & o_d;
-                            const uint32_t below = pad ? ((2u << (31 - __builtin_clz(pad))) - 1u) : 0u;
-                            go = (o_d & below) == pad;
+                            go = first_padding(S, o_d);                         // quirk Q1 duplicates
                         }
                         if (!__any(go)) continue;
                         st_evals += (uint32_t)__popcll(__ballot(go)); ++st_passes;
@@ -377,14 +354,7 @@ __global__ void __launch_bounds__(64, 3) p2s_tri_fused_kernel(const P2sTriArgs a
 
 template <typename T, int CT, int TPW>
 hipError_t launch_fused(P2sTriArgs a, int singles_pct, hipStream_t s) {
-    const int64_t n_units = a.n_blocks * a.K;
-    const int64_t n_tiles = (n_units + 63) / 64;
-    const int64_t per_xcd = (n_tiles + 7) / 8;
-    int64_t singles = per_xcd * singles_pct / 100;
-    singles += (per_xcd - singles) % TPW;                      // the rest in whole groups of TPW
-    a.pool_singles = (uint32_t)singles;
-    a.pool_pairs = (uint32_t)((per_xcd - singles) / TPW);
-    const unsigned grid = (unsigned)(8 * (a.pool_pairs + a.pool_singles));
+    const unsigned grid = deal_grid(a, singles_pct, TPW);
     if (a.C == CT)
         hipLaunchKernelGGL((p2s_tri_fused_kernel<T, CT, true, TPW>), dim3(grid), dim3(64), 0, s, a);
     else

@@ -40,12 +40,6 @@
 
 namespace {
 
-#ifndef P2S_POOL_SLOTS4
-#define P2S_POOL_SLOTS4 32
-#endif
-#ifndef P2S_POOL_WIDE_REREAD
-#define P2S_POOL_WIDE_REREAD 0       // 9-16 cameras: 1 = x and y are read again for the reprojection pass instead of kept (32 registers)
-#endif
 #ifndef P2S_POOL_WIDE_STREAM
 #define P2S_POOL_WIDE_STREAM 0
 #endif
@@ -57,7 +51,6 @@ namespace {
 #ifndef P2S_POOL_WPS
 #define P2S_POOL_WPS 3          // waves per SIMD the register allocation aims at
 #endif
-constexpr uint32_t kNone = 0xffffffffu;
 constexpr float kInfF = __builtin_huge_valf();
 
 // Up to 8 cameras tier B builds a survivor's normal matrix from the unit's observations (8 cameras accumulated cost less
@@ -75,16 +68,6 @@ struct alignas(16) QSlot : SlotNormal<(CT > 8)> {
     uint32_t nan, zero;
     uint32_t unit;                         // unit index within the chunk
     uint32_t surv;                         // the current level's screen let somebody through
-};
-
-template <typename T>
-struct SlotObs {
-    const T *o;
-    double lik_thr;
-    __device__ __forceinline__ void raw(int c, double &x, double &y, double &wo) const {
-        x = (double)o[3 * c]; y = (double)o[3 * c + 1]; wo = 0.0;
-    }
-    __device__ __forceinline__ void rawT(int c, T &x, T &y, T &wo) const { x = o[3 * c]; y = o[3 * c + 1]; wo = o[3 * c + 2]; }
 };
 
 template <typename T, int CT, bool EXACT>
@@ -110,7 +93,7 @@ __device__ __forceinline__ void load_obs(const P2sTriArgs &a, int C, uint32_t b,
 
 // Cameras c0 .. c0 + 7 of one unit (the 9-16 camera kernels work on the observations eight cameras at a time: 48 registers
 // of observations beside the eigen-solve spilled ~400 B per lane in round 2).
-template <typename T, bool EXACT, bool WITH_W = true, bool STREAM = true>
+template <typename T, bool EXACT, bool STREAM = true>
 __device__ __forceinline__ void load_half(const P2sTriArgs &a, int C, uint32_t b, uint32_t k, int c0, RegObs<T, 8> &obs) {
     const unsigned char *chunk = reinterpret_cast<const unsigned char *>(a.xyl) +
                                  (size_t)a.block0 * (size_t)C * (size_t)a.K * 3u * sizeof(T);
@@ -120,22 +103,14 @@ __device__ __forceinline__ void load_half(const P2sTriArgs &a, int C, uint32_t b
     for (int i = 0; i < 8; ++i) {
         const bool there = EXACT || c0 + i < C;
         const T *p = reinterpret_cast<const T *>(chunk + (size_t)(there ? c0 + i : 0) * cam_stride + voff);
-        T x, y, w = (T)0;
+        T x, y, w;
         if (STREAM) {
-            x = __builtin_nontemporal_load(p); y = __builtin_nontemporal_load(p + 1);
-            if (WITH_W) w = __builtin_nontemporal_load(p + 2);
+            x = __builtin_nontemporal_load(p); y = __builtin_nontemporal_load(p + 1); w = __builtin_nontemporal_load(p + 2);
         } else {                                                   // read again later: let the caches keep the lines
-            x = p[0]; y = p[1];
-            if (WITH_W) w = p[2];
+            x = p[0]; y = p[1]; w = p[2];
         }
         obs.x[i] = there ? x : (T)0; obs.y[i] = there ? y : (T)0; obs.w[i] = there ? w : (T)0;
     }
-}
-
-__device__ __forceinline__ void wsync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // ---- tier A arithmetic (fp32, TWO candidates per lane in the halves of packed registers) ---------------------------------
@@ -219,7 +194,8 @@ __global__ void __launch_bounds__(64, P2S_POOL_WPS) p2s_tri_pool_kernel(const P2
     // (frame, camera) runs two neighbouring tiles share are fetched into one L2 only; within it the first workgroups take
     // TPW tiles each (tiles xj, xj + n, xj + 2n of the range, n = such workgroups per XCD: neighbouring tiles are streamed
     // by neighbouring workgroups at about the same time) and the last ones a single tile: the waves that start last are
-    // the short ones, so the grid drains quickly.
+    // the short ones, so the grid drains quickly.  (deal_grid of p2s_tri_dev.h is the host's side.  The same lines stand
+    // in p2s_tri_fused.hip: behind a shared helper this kernel's registers were allocated differently.)
     const uint32_t per_xcd = (n_tiles + 7u) >> 3;
     const uint32_t xj = blockIdx.x >> 3;
     if (xj >= a.pool_pairs + a.pool_singles) return;
@@ -244,11 +220,6 @@ __global__ void __launch_bounds__(64, P2S_POOL_WPS) p2s_tri_pool_kernel(const P2
     int n_used = 0, n_over = 0;                          // slots in use, units waiting in sOver (wave-uniform)
     uint32_t st_units = 0, st_evals = 0, st_passes = 0, st_screened = 0, st_spasses = 0;
 
-    auto unit_of = [&](uint32_t t, bool &active) -> uint32_t {
-        const int64_t lu = ((int64_t)t << 6) + lane;
-        active = lu < n_units;
-        return active ? (uint32_t)lu : (uint32_t)(t << 6);
-    };
     // A slot keeps what the screen needs of level 0 -- its base: N' = T^T N T about c0 = the level-0 point, in fp64 and
     // then rounded (g and h are what is left of M c0 + b and c0.(M c0 + 2b) + c after cancellation) -- and the unit's
     // observations; tier B builds its normal matrices from those.
@@ -442,10 +413,7 @@ __global__ void __launch_bounds__(64, P2S_POOL_WPS) p2s_tri_pool_kernel(const P2
                         if (go) {
                             // level 1 is rank r <-> camera r (itertools.combinations order); the deeper levels go to the table
                             S = (level == 1) ? (1u << r) : (uint32_t)a.sub_tab[sub0 + r];
-                            // quirk Q1 duplicates: only the lexicographically first padding can win the argmin
-                            const uint32_t pad = S & o_d;
-                            const uint32_t below = pad ? ((2u << (31 - __builtin_clz(pad))) - 1u) : 0u;
-                            go = (o_d & below) == pad;
+                            go = first_padding(S, o_d);                                // quirk Q1 duplicates
                         }
                         return S;
                     };
@@ -746,12 +714,12 @@ __global__ void __launch_bounds__(64, P2S_POOL_WPS) p2s_tri_pool_kernel(const P2
     auto level0_wide = [&](const int t) {
         const uint32_t tile = tile0 + (uint32_t)t * tstride;
         bool act;
-        const uint32_t u = unit_of(tile, act);
+        const uint32_t u = unit_of(tile, lane, n_units, act);
         const uint32_t ub = u / (uint32_t)K, uk = u % (uint32_t)K;
         RegObs<T, 8> h0, h1;
         h0.lik_thr = a.lik_thr; h1.lik_thr = a.lik_thr;
-        load_half<T, EXACT, true, P2S_POOL_WIDE_STREAM != 0>(a, C, ub, uk, 0, h0);
-        load_half<T, EXACT, true, P2S_POOL_WIDE_STREAM != 0>(a, C, ub, uk, 8, h1);
+        load_half<T, EXACT, P2S_POOL_WIDE_STREAM != 0>(a, C, ub, uk, 0, h0);
+        load_half<T, EXACT, P2S_POOL_WIDE_STREAM != 0>(a, C, ub, uk, 8, h1);
         double N[10];
 #pragma unroll
         for (int i = 0; i < 10; ++i) N[i] = 0.0;
@@ -780,10 +748,6 @@ __global__ void __launch_bounds__(64, P2S_POOL_WPS) p2s_tri_pool_kernel(const P2
         double q[3];
         smallest_eigvec(N, q);
         uint32_t ub2 = ub;
-#if P2S_POOL_WIDE_REREAD
-        asm volatile("" : "+v"(ub2) : "v"(q[0]));                          // the second read not before the eigen-solve
-        load_half<T, EXACT, false>(a, C, ub2, uk, 0, h0);                  // x and y only
-#endif
         if (C - V < 2) { q[0] = d_nan(); q[1] = d_nan(); q[2] = d_nan(); }
         double sum = 0.0;
         bool irregular = false;
@@ -800,13 +764,7 @@ __global__ void __launch_bounds__(64, P2S_POOL_WPS) p2s_tri_pool_kernel(const P2
             }
         };
         distances(0, h0);
-#if P2S_POOL_WIDE_REREAD
-        asm volatile("" : "+v"(ub2));                                      // (addresses are recomputed, not kept: 2 registers per camera)
-        load_half<T, EXACT, false>(a, C, ub2, uk, 8, h0);
-        distances(8, h0);
-#else
         distances(8, h1);
-#endif
         if (__any(irregular)) {                                            // rare: some wanted camera is degenerate / NaN
             double sum2 = 0.0;
             auto exact = [&](const int c0, const RegObs<T, 8> &h) {
@@ -818,15 +776,8 @@ __global__ void __launch_bounds__(64, P2S_POOL_WPS) p2s_tri_pool_kernel(const P2
                     }
                 }
             };
-#if P2S_POOL_WIDE_REREAD
-            load_half<T, EXACT, false>(a, C, ub2, uk, 0, h0);
-            exact(0, h0);
-            load_half<T, EXACT, false>(a, C, ub2, uk, 8, h0);
-            exact(8, h0);
-#else
             exact(0, h0);
             exact(8, h1);
-#endif
             sum = irregular ? sum2 : sum;
         }
         const double e = sum * fast_rcp((double)__popc(valid));
@@ -878,7 +829,7 @@ __global__ void __launch_bounds__(64, P2S_POOL_WPS) p2s_tri_pool_kernel(const P2
     obs4.lik_thr = a.lik_thr; obs5.lik_thr = a.lik_thr;
     bool act0, act1 = false, act2 = false, act3 = false, act4 = false, act5 = false;
     if constexpr (CT <= 8) {
-        const uint32_t u0 = unit_of(tile0, act0);
+        const uint32_t u0 = unit_of(tile0, lane, n_units, act0);
         load_obs<T, CT, EXACT>(a, C, u0 / (uint32_t)K, u0 % (uint32_t)K, obs0);
     } else {
         act0 = false;
@@ -890,7 +841,7 @@ __global__ void __launch_bounds__(64, P2S_POOL_WPS) p2s_tri_pool_kernel(const P2
     const bool six = TPW > 5 && my_tiles > 5 && tile0 + 5 * tstride < n_tiles;
     auto request = [&](const bool wanted, const int t, bool &act, RegObs<T, CT> &obs, double dep) {
         if (wanted) {
-            uint32_t u = unit_of(tile0 + (uint32_t)t * tstride, act);
+            uint32_t u = unit_of(tile0 + (uint32_t)t * tstride, lane, n_units, act);
             asm volatile("" : "+v"(u) : "v"(dep));                         // not before the eigen-solve
             load_obs<T, CT, EXACT>(a, C, u / (uint32_t)K, u % (uint32_t)K, obs);
         }
@@ -935,20 +886,9 @@ __global__ void __launch_bounds__(64, P2S_POOL_WPS) p2s_tri_pool_kernel(const P2
     }
 }
 
-}  // namespace
-
-namespace {
-
 template <typename T, int CT, int NSLOT, int TPW>
 hipError_t launch_pool(P2sTriArgs a, int singles_pct, hipStream_t s) {
-    const int64_t n_units = a.n_blocks * a.K;
-    const int64_t n_tiles = (n_units + 63) / 64;
-    const int64_t per_xcd = (n_tiles + 7) / 8;
-    int64_t singles = per_xcd * singles_pct / 100;
-    singles += (per_xcd - singles) % TPW;                      // the rest in whole groups of TPW
-    a.pool_singles = (uint32_t)singles;
-    a.pool_pairs = (uint32_t)((per_xcd - singles) / TPW);
-    const unsigned grid = (unsigned)(8 * (a.pool_pairs + a.pool_singles));
+    const unsigned grid = deal_grid(a, singles_pct, TPW);
     if (a.C == CT)
         hipLaunchKernelGGL((p2s_tri_pool_kernel<T, CT, NSLOT, true, TPW>), dim3(grid), dim3(64), 0, s, a);
     else
