@@ -301,6 +301,33 @@ int p2s_jitter_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, const
 /* Milliseconds the kernels of this context's last p2s_jitter_host took (HIP events around them). */
 int p2s_jitter_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
 
+/* ---- np.mean and np.std of columns ------------------------------------------------------------------------------------
+ * For each of n_cols contiguous float64 columns of n_rows entries (column-major, as p2s_column_order_stats_host takes
+ * them), NaN entries skipped: counts[c] = the number m of non-NaN entries, mean[c] = np.mean and std[c] = np.std (ddof 0)
+ * of those entries in row order, bit for bit: the sum is np.add.reduce's -- chunks of 8192 entries added left to right,
+ * each summed pairwise over blocks of at most 128 with eight accumulators -- the deviations are squared after one
+ * rounded subtraction, and the root is correctly rounded.  NaN for a column without entries.  n_rows < 2^31; any output
+ * may be NULL.  HOST pointers; blocks. */
+int p2s_column_mean_std_host(p2s_ctx *ctx, int64_t n_rows, int32_t n_cols, const double *data, double *mean, double *std,
+                             int64_t *counts);
+
+/* ---- 2D confidence statistics (Utilities/pose_confidence_analyze.py:118-219) ----------------------------------------------
+ * compute_statistics, compute_band_distribution and simulate_threshold for every camera at once, float64 and bit for bit
+ * the reference's numbers.  tables: the cameras' [n_frames[c]][n_kpts] confidences back to back, NaN = no person in the
+ * frame; 1 <= n_frames[c] < 2^31, 1 <= n_kpts <= 64, n_thresholds <= 8.  Per (camera, keypoint), over the non-NaN entries
+ * in frame order (any output may be NULL):
+ *   stats   [n_cams][n_kpts][9]  np.mean, np.median, np.std, min, max, np.percentile at 5, 25, 75 and 95; NaN without entries
+ *   counts  [n_cams][n_kpts]     the number of entries
+ *   below   [n_thresholds][n_cams][n_kpts]  entries < thresholds[t]
+ *   bands   [n_cams][n_kpts][5]  entries in [0, 0.4), [0.4, 0.6), [0.6, 0.8), [0.8, 1.0] (closed) and [1.0, inf): 1.0 counts
+ *                                twice, a negative entry and +inf in none
+ * The rates the reference reports are these counts divided by `counts`.  HOST pointers; blocks. */
+int p2s_confidence_stats_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, int32_t n_kpts, const double *tables,
+                              int32_t n_thresholds, const double *thresholds, double *stats, int64_t *counts, int64_t *below,
+                              int64_t *bands);
+/* Milliseconds the kernels of this context's last p2s_confidence_stats_host took (HIP events around them). */
+int p2s_confidence_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
+
 /* ---- synchronization (synchronize_cams_all, synchronization.py:1346-1612) ------------------------------------------
  * Speeds: replaces the per-camera pandas / scipy work of :1562-1584 (interpolate_zeros_nans :1565, bfill().ffill(),
  * signal.filtfilt :1568, vert_speed :1271-1288, abs().sum(axis=1) :1579, filtfilt of the sum :1585).  coords: the cameras'

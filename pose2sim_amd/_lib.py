@@ -93,6 +93,9 @@ SIGNATURES = {
                         + [C.c_void_p] * 7 + [C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
     'p2s_jitter_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     'p2s_json_select_tracked_person': (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'p2s_column_mean_std_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'p2s_confidence_stats_host': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5),
+    'p2s_confidence_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     'p2s_timing_begin': (C.c_int, [C.c_void_p]),
     'p2s_timing_end': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     'p2s_json_parse': (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]),
@@ -119,7 +122,8 @@ SIGNATURES = {
 # entry points a library built before them lacks (P2S_LIB may name one): left unbound, and the feature is refused
 OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_host', 'p2s_json_gather_largest_person',
             'p2s_copy_files', 'p2s_reproject_host', 'p2s_reproject_kernel_ms', 'p2s_write_openpose_files',
-            'p2s_column_order_stats_host', 'p2s_jitter_host', 'p2s_jitter_kernel_ms', 'p2s_json_select_tracked_person'}
+            'p2s_column_order_stats_host', 'p2s_jitter_host', 'p2s_jitter_kernel_ms', 'p2s_json_select_tracked_person',
+            'p2s_column_mean_std_host', 'p2s_confidence_stats_host', 'p2s_confidence_kernel_ms'}
 
 _lib = None
 

@@ -1,7 +1,8 @@
 // What more than one translation unit needs: the device-resident camera, the counter and work-list constants, and what
 // the triangulation entry points (p2s_tri.hip) share with the kernels they drive in other files -- P2sTriArgs, the deep
-// rounds (p2s_tri_deep.hip) and the one-launch kernels (p2s_tri_fused.hip, p2s_tri_pool.hip).  Every other argument
-// struct stands in its stage's own .hip file, beside the kernels and the entry points.
+// rounds (p2s_tri_deep.hip) and the one-launch kernels (p2s_tri_fused.hip, p2s_tri_pool.hip) -- and P2sOrderArgs, the
+// exact order statistic of p2s_jitter.hip that p2s_confidence.hip launches as well.  Every other argument struct stands
+// in its stage's own .hip file, beside the kernels and the entry points.
 #ifndef P2S_INTERNAL_H
 #define P2S_INTERNAL_H
 
@@ -126,5 +127,22 @@ hipError_t p2s_launch_tri_fused(const P2sTriArgs &a, int dtype, int singles_pct,
 // p2s_tri_pool.hip: persistent waves, failures pooled across tiles, fp32 screen + fp64 evaluation of the survivors
 bool p2s_tri_pool_supports(int C, int dtype, int undistort, int lr_swap);
 hipError_t p2s_launch_tri_pool(const P2sTriArgs &a, int dtype, int singles_pct, int tiles_per_wave, hipStream_t s);
+
+// exact order statistics of fp64 columns, NaN skipped (np.nanmedian and its kin): order_stats_kernel of p2s_jitter.hip,
+// which p2s_confidence.hip launches too
+struct P2sOrderArgs {
+    const double *data;
+    const int64_t *col_off;      // [n_cols] first element of every column, or NULL: col * n_rows
+    const int64_t *col_len;      // [n_cols] length of every column, or NULL: n_rows
+    const int64_t *ranks;        // [n_ranks] 0-based ranks among the non-NaN entries, negative = from the top; NULL: the
+                                 // two middle positions (m - 1) / 2 and m / 2 of every column (n_ranks is taken as 2)
+    const double *fractions;     // [n_ranks / 2] when set (ranks is ignored): ranks 2i and 2i + 1 of a column with m entries
+                                 // are lo = floor((m - 1) * fractions[i]) and min(lo + 1, m - 1), np.percentile's neighbours
+    double *out;                 // [n_cols][n_ranks]; NaN for a rank outside [0, m)
+    int64_t *counts;             // [n_cols] non-NaN entries m, or NULL
+    int64_t n_rows;
+    int32_t n_cols, n_ranks;
+};
+hipError_t p2s_launch_order_stats(const P2sOrderArgs &a, hipStream_t s);
 
 #endif

@@ -24,19 +24,6 @@
 
 #pragma clang fp contract(off)
 
-// exact order statistics of fp64 columns, NaN skipped (np.nanmedian and its kin)
-struct P2sOrderArgs {
-    const double *data;
-    const int64_t *col_off;      // [n_cols] first element of every column, or NULL: col * n_rows
-    const int64_t *col_len;      // [n_cols] length of every column, or NULL: n_rows
-    const int64_t *ranks;        // [n_ranks] 0-based ranks among the non-NaN entries, negative = from the top; NULL: the
-                                 // two middle positions (m - 1) / 2 and m / 2 of every column (n_ranks is taken as 2)
-    double *out;                 // [n_cols][n_ranks]; NaN for a rank outside [0, m)
-    int64_t *counts;             // [n_cols] non-NaN entries m, or NULL
-    int64_t n_rows;
-    int32_t n_cols, n_ranks;
-};
-
 // 2D keypoint jitter analysis (Utilities/keypoint_jitter_analyze.py:143-325).  Cameras back to back:
 // camera c holds frames frame_off[c] .. frame_off[c + 1] and one displacement row fewer than frames, so its first row
 // among all rows is frame_off[c] - c.
@@ -246,7 +233,7 @@ __global__ void __launch_bounds__(OS_THREADS) order_stats_kernel(const P2sOrderA
     const int col = blockIdx.x, tid = threadIdx.x;
     const double *x = a.data + (a.col_off ? a.col_off[col] : (int64_t)col * a.n_rows);
     const int64_t n = a.col_len ? a.col_len[col] : a.n_rows;
-    const int n_ranks = a.ranks ? a.n_ranks : 2;
+    const int n_ranks = (a.ranks || a.fractions) ? a.n_ranks : 2;
     double *out = a.out + (int64_t)col * n_ranks;
 
     os_histogram(s, x, n, 56, 0);
@@ -261,7 +248,10 @@ __global__ void __launch_bounds__(OS_THREADS) order_stats_kernel(const P2sOrderA
     uint32_t less = 0, equal = 0;
     for (int j = 0; j < n_ranks; ++j) {
         int64_t r;
-        if (a.ranks) { r = a.ranks[j]; if (r < 0) r += m; }      // negative: counted from the top
+        if (a.fractions) {                                        // np.percentile's lo, hi around (m - 1) * fraction
+            const int64_t lo = (int64_t)floor((double)((int64_t)m - 1) * a.fractions[j >> 1]);
+            r = (j & 1) ? (lo + 1 < (int64_t)m ? lo + 1 : (int64_t)m - 1) : lo;
+        } else if (a.ranks) { r = a.ranks[j]; if (r < 0) r += m; }   // negative: counted from the top
         else r = j == 0 ? ((int64_t)m - 1) / 2 : (int64_t)m / 2;  // the two middle positions (equal when m is odd)
         if (m == 0 || r < 0 || r >= (int64_t)m) {
             if (tid == 0) out[j] = jt_nan();
@@ -437,7 +427,7 @@ __global__ void __launch_bounds__(1024) scan_tiles_kernel(const P2sJitterArgs a)
 
 }  // namespace
 
-static hipError_t p2s_launch_order_stats(const P2sOrderArgs &a, hipStream_t s) {
+hipError_t p2s_launch_order_stats(const P2sOrderArgs &a, hipStream_t s) {   // also p2s_confidence.hip
     if (a.n_cols == 0) return hipSuccess;
     hipLaunchKernelGGL(order_stats_kernel, dim3((unsigned)a.n_cols), dim3(OS_THREADS), 0, s, a);
     return hipGetLastError();

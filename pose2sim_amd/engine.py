@@ -412,6 +412,58 @@ class Engine:
         _lib.check(fn(self._h, C.byref(ms)))
         return ms.value
 
+    # -- np.mean / np.std of columns; 2D confidence statistics (Utilities/pose_confidence_analyze.py:118-219) ------------
+    def column_mean_std(self, data):
+        """data [n_rows][n_cols] float64 (any strides; NaN entries are skipped).  -> (mean [n_cols], std [n_cols], counts
+        [n_cols]): np.mean and np.std of every column's non-NaN entries in row order, bit for bit (NumPy's own summation
+        order), NaN for a column without entries."""
+        fn = _entry(self._lib, 'p2s_column_mean_std_host')
+        data = np.asarray(data, dtype=np.float64)
+        if data.ndim != 2:
+            raise P2sError(f'data has shape {data.shape}; expected [n_rows][n_cols]')
+        cols = np.ascontiguousarray(data.T)                       # the library takes the columns contiguous
+        n_cols, n_rows = cols.shape
+        mean, std = np.empty(n_cols), np.empty(n_cols)
+        counts = np.zeros(n_cols, dtype=np.int64)
+        _lib.check(fn(self._h, n_rows, n_cols, _optr(cols), _optr(mean), _optr(std), _optr(counts)))
+        return mean, std, counts
+
+    CONFIDENCE_STATS = ('mean', 'median', 'std', 'min', 'max', 'p5', 'p25', 'p75', 'p95')
+    CONFIDENCE_BANDS = ('low', 'danger', 'medium', 'high', 'very_high')
+
+    def confidence_stats(self, tables, thresholds=(0.4,)):
+        """tables: one [n_frames][K] float64 confidence table per camera (NaN rows = no person; lengths may differ, each
+        >= 1; K <= 64), thresholds: up to 8.  Per (camera, keypoint) over the non-NaN entries in frame order -> dict:
+        'stats' [C][K][9] (CONFIDENCE_STATS: np.mean, np.median, np.std, min, max, np.percentile 5 / 25 / 75 / 95; NaN
+        without entries), 'counts' [C][K] int64, 'below' [T][C][K] int64 entries < threshold, 'below_rate' [T][C][K]
+        (NaN without entries), 'bands' [C][K][5] int64 (CONFIDENCE_BANDS: [0, 0.4), [0.4, 0.6), [0.6, 0.8), [0.8, 1.0]
+        closed, [1.0, inf)), 'band_rate' [C][K][5] (0.0 without entries)."""
+        fn = _entry(self._lib, 'p2s_confidence_stats_host')
+        tables = [np.ascontiguousarray(t, dtype=np.float64) for t in tables]
+        if not tables or any(t.ndim != 2 or t.shape[1] != tables[0].shape[1] or len(t) < 1 for t in tables):
+            raise P2sError('every camera needs an [n_frames >= 1][K] table with the same K')
+        Cn, K = len(tables), tables[0].shape[1]
+        n_frames = np.array([len(t) for t in tables], dtype=np.int64)
+        flat = tables[0] if Cn == 1 else np.concatenate(tables)
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        stats = np.empty((Cn, K, 9))
+        counts = np.zeros((Cn, K), dtype=np.int64)
+        below = np.zeros((len(thr), Cn, K), dtype=np.int64)
+        bands = np.zeros((Cn, K, 5), dtype=np.int64)
+        _lib.check(fn(self._h, Cn, _ptr(n_frames), K, _optr(flat), len(thr), _optr(thr), _optr(stats), _optr(counts), _optr(below),
+                      _optr(bands)))
+        with np.errstate(invalid='ignore', divide='ignore'):
+            below_rate = below / counts                           # int64 / int64: the correctly rounded quotient, 0 / 0 = NaN
+            band_rate = np.where(counts[:, :, None] > 0, bands / counts[:, :, None], 0.0)
+        return {'stats': stats, 'counts': counts, 'below': below, 'below_rate': below_rate, 'bands': bands, 'band_rate': band_rate}
+
+    def confidence_kernel_ms(self):
+        """Kernel time of the last confidence_stats() call, from HIP events around its kernels."""
+        fn = _entry(self._lib, 'p2s_confidence_kernel_ms')
+        ms = C.c_float(0)
+        _lib.check(fn(self._h, C.byref(ms)))
+        return ms.value
+
     # -- synchronization (synchronization.py:1271-1343, 1541-1585) -------------------------------------------------------
     def sync_speeds(self, coords, b, a, zi):
         """coords: one [n_frames][n_cols] array per camera, the (x, y) columns of the keypoints to consider with the
