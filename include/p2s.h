@@ -328,6 +328,45 @@ int p2s_confidence_stats_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_fra
 /* Milliseconds the kernels of this context's last p2s_confidence_stats_host took (HIP events around them). */
 int p2s_confidence_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
 
+/* ---- linear_sum_assignment (scipy.optimize, 1.15.3) --------------------------------------------------------------------
+ * n cost matrices [n_rows][n_cols] row-major back to back, 1 <= n_rows, n_cols <= 32.  Per matrix: status = 0 and the
+ * min(n_rows, n_cols) assigned (row, column) pairs in ascending row order, exactly scipy's (row_ind, col_ind), ties
+ * included (csrc/p2s_lsap.h lists the decisions that make it so); status = 1 for a matrix holding NaN or -inf (scipy:
+ * 'matrix contains invalid numeric entries'), 2 for one without a finite assignment ('cost matrix is infeasible'), the
+ * pairs then -1.  row_ind, col_ind [n][min(n_rows, n_cols)], status [n].  With a context the matrices are solved on the
+ * GPU, one a wave; ctx == NULL solves them on the host with the same code (the restatement can be checked without a GPU).
+ * HOST pointers; blocks. */
+int p2s_lsap_host(p2s_ctx *ctx, int64_t n, int32_t n_rows, int32_t n_cols, const double *cost, int32_t *row_ind, int32_t *col_ind,
+                  int32_t *status);
+
+/* ---- frame-to-frame person matching (Utilities/id_switch_analyze.py:47-145, 148-291, 364-388) -----------------------------
+ * For every camera at once, float64 and bit for bit the reference's numbers.  Camera c has n_frames[c] >= 0 frames (the
+ * readable files, in order); the frames of all cameras stand back to back.  persons [N][26][3] (x, y, confidence): every
+ * listed person of every frame in that order; person_off [frames + 1]: the first person of every frame, person_off[0] = 0.
+ * A person is kept when some confidence is above 0 (parse_frame_people).  Per frame f, camera-local indices:
+ *   tables [7][frames] int32
+ *     0 count       kept persons
+ *     1 prev        the last earlier frame of the camera with a kept person, -1 without one (prev_people)
+ *     2 zero_run    the frames between the two, f - 1 - prev (zero_count on reaching f)
+ *     3 n_matched   pairs of linear_sum_assignment over the mean-keypoint-distance matrix (compute_match_cost: keypoints
+ *                   with both confidences above 0.1, fewer than 3 of them cost 1e9) whose cost is below 1e9; 0 for a
+ *                   frame without kept persons or without a previous frame
+ *     4 n_lost      kept persons of the previous frame left unmatched
+ *     5 n_appeared  kept persons of this frame left unmatched
+ *     6 flag        0; 1 / 2 = the cost matrix is refused as by p2s_lsap_host (a NaN coordinate on a shared keypoint);
+ *                   4 = more than 32 kept persons in the frame or its previous one: not matched
+ *   kept [N] int32         from person_off[f]: the frame's `count` kept persons in list order, as indices into the frame's
+ *                          own list; the rest of the frame's run is unspecified
+ *   distances     the matched costs, per camera in frame order and within a frame in previous-person order, the cameras
+ *                 back to back; room for N values covers every case
+ *   n_distances [n_cams]   how many of them each camera has
+ *   stats [n_cams][6]      np.mean, np.median, np.percentile 95 and 99, min and max of the camera's distances; NaN without
+ * Any output may be NULL.  HOST pointers; blocks. */
+int p2s_id_switch_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, const int64_t *person_off, const double *persons,
+                       int32_t *tables, int32_t *kept, double *distances, int64_t *n_distances, double *stats);
+/* Milliseconds the kernels of this context's last p2s_id_switch_host took (HIP events around them). */
+int p2s_id_switch_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
+
 /* ---- synchronization (synchronize_cams_all, synchronization.py:1346-1612) ------------------------------------------
  * Speeds: replaces the per-camera pandas / scipy work of :1562-1584 (interpolate_zeros_nans :1565, bfill().ffill(),
  * signal.filtfilt :1568, vert_speed :1271-1288, abs().sum(axis=1) :1579, filtfilt of the sum :1585).  coords: the cameras'
@@ -454,6 +493,23 @@ int p2s_json_free(p2s_json_batch *batch);
 int p2s_json_people_counts(const p2s_json_batch *batch, int32_t *counts, int64_t *person_base);
 /* lengths [person_base[n_files]]: len(person['pose_keypoints_2d']) or a P2S_JSON_PERSON_* code. */
 int p2s_json_person_lengths(const p2s_json_batch *batch, int32_t *lengths);
+/* The "person_id" value of every person (file-major, as p2s_json_person_lengths), as the raw JSON text of the value:
+ * text_off [person_base[n_files] + 1] byte offsets into text, an empty text = the person has no such key (a repeated key
+ * takes the last value).  text may be NULL: then only text_off is filled (text_off's last entry is the size to provide).
+ * file_kind [n_files] (may be NULL): why a file has no person list, which the people counts do not tell apart --
+ * what the reference's data.get('people', []) and the loop over it do with the document. */
+#define P2S_JSON_DOC_UNREADABLE (-1)      /* P2S_JSON_UNREADABLE                                                    */
+#define P2S_JSON_DOC_PEOPLE 0             /* an object whose "people" is a list                                     */
+#define P2S_JSON_DOC_NO_PEOPLE_KEY 1      /* an object without "people": .get's default, no person                  */
+#define P2S_JSON_DOC_PEOPLE_NULL 2        /* "people": null -- iterating None raises TypeError                      */
+#define P2S_JSON_DOC_PEOPLE_OTHER 3       /* "people" is a number, a string, an object, true or false               */
+#define P2S_JSON_DOC_LIST 4               /* the document is no object: .get raises AttributeError on a list, ...   */
+#define P2S_JSON_DOC_STRING 5             /* ... a str,                                                             */
+#define P2S_JSON_DOC_INT 6                /* ... an int,                                                            */
+#define P2S_JSON_DOC_FLOAT 7              /* ... a float (NaN and the infinities included),                         */
+#define P2S_JSON_DOC_BOOL 8               /* ... a bool,                                                            */
+#define P2S_JSON_DOC_NULL 9               /* ... None                                                               */
+int p2s_json_person_ids(const p2s_json_batch *batch, int64_t *text_off, char *text, int64_t text_capacity, int32_t *file_kind);
 /* extract_files_frame_f for every file at once: for file i and person n < max_persons writes
  * out[file_offsets[i] + n*person_stride + 3*k + {0,1,2}] = values[3*keypoint_ids[k] + {0,1,2}], NaN when
  * the file, the person or the triplet does not exist (triangulation.py:629-644); file_offsets[i] < 0 skips

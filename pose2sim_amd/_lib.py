@@ -18,6 +18,11 @@ P2S_JSON_UNREADABLE, P2S_JSON_NO_PEOPLE_LIST = -1, -2
 P2S_ERR_INVALID_ARG = -1
 P2S_ERR_GCV_SHORT_RUN, P2S_ERR_GCV_ILL_POSED, P2S_ERR_GCV_NO_MINIMUM, P2S_ERR_GCV_SINGULAR = -6, -7, -8, -9
 P2S_JSON_PERSON_NO_LIST, P2S_JSON_PERSON_NOT_NUMERIC = -1, -2
+P2S_JSON_DOC_UNREADABLE, P2S_JSON_DOC_PEOPLE, P2S_JSON_DOC_NO_PEOPLE_KEY, P2S_JSON_DOC_PEOPLE_NULL, P2S_JSON_DOC_PEOPLE_OTHER = -1, 0, 1, 2, 3
+P2S_JSON_DOC_TYPES = {4: 'list', 5: 'str', 6: 'int', 7: 'float', 8: 'bool', 9: 'NoneType'}    # P2S_JSON_DOC_LIST .. P2S_JSON_DOC_NULL
+P2S_LSAP_MAX = 32
+P2S_LSAP_ERRORS = {1: 'matrix contains invalid numeric entries', 2: 'cost matrix is infeasible'}   # scipy's messages
+P2S_IDS_TOO_MANY = 4
 P2S_ERR_SYNC_PADLEN = -10
 P2S_REPROJ_DISTORTED = 1
 P2S_TRACK_SELECTED, P2S_TRACK_NO_PEOPLE, P2S_TRACK_NO_CANDIDATE = 1, 0, 2
@@ -96,6 +101,10 @@ SIGNATURES = {
     'p2s_column_mean_std_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'p2s_confidence_stats_host': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5),
     'p2s_confidence_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    'p2s_lsap_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
+    'p2s_id_switch_host': (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 8),
+    'p2s_id_switch_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    'p2s_json_person_ids': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'p2s_timing_begin': (C.c_int, [C.c_void_p]),
     'p2s_timing_end': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     'p2s_json_parse': (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]),
@@ -123,7 +132,8 @@ SIGNATURES = {
 OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_host', 'p2s_json_gather_largest_person',
             'p2s_copy_files', 'p2s_reproject_host', 'p2s_reproject_kernel_ms', 'p2s_write_openpose_files',
             'p2s_column_order_stats_host', 'p2s_jitter_host', 'p2s_jitter_kernel_ms', 'p2s_json_select_tracked_person',
-            'p2s_column_mean_std_host', 'p2s_confidence_stats_host', 'p2s_confidence_kernel_ms'}
+            'p2s_column_mean_std_host', 'p2s_confidence_stats_host', 'p2s_confidence_kernel_ms', 'p2s_lsap_host',
+            'p2s_id_switch_host', 'p2s_id_switch_kernel_ms', 'p2s_json_person_ids'}
 
 _lib = None
 

@@ -324,6 +324,14 @@ hipError_t launch_confidence(const P2sConfArgs &a, hipStream_t s) {
 
 }  // namespace
 
+hipError_t p2s_launch_column_moments(const double *cols, double *valid, int64_t n_rows, int32_t n_cols, int64_t *m, double *minmax,
+                                     double *mean_std, hipStream_t s) {   // also p2s_idswitch.hip
+    P2sConfArgs a{};
+    a.cols = const_cast<double *>(cols); a.valid = valid; a.m = m; a.minmax = minmax; a.mean_std = mean_std;
+    a.n_rows = n_rows; a.n_cols = n_cols;
+    return launch_columns(a, s);
+}
+
 // ---- C-ABI entry points (include/p2s.h) ----------------------------------------------------------------------------
 extern "C" {
 

@@ -41,13 +41,16 @@ enum PersonStatus : int8_t {
 };
 
 enum : int8_t { kPersonNotObject = 1, kPersonHasNull = 2 };                    // Person::flags
-enum : int8_t { kFileTopObject = 1, kFilePeopleNull = 2, kFilePeopleOther = 4 };  // FileRec::flags
+enum : int8_t { kFileTopObject = 1, kFilePeopleNull = 2, kFilePeopleOther = 4 };  // FileRec::flags; bits 3..5: kFileTopShift
+constexpr int kFileTopShift = 3;      // (P2S_JSON_DOC_LIST .. P2S_JSON_DOC_NULL) - P2S_JSON_DOC_LIST + 1 of a document that is no object
 
 struct Person {
     int64_t off;
     int32_t len;
     int8_t status;
     int8_t flags;         // what the status does not tell apart (p2s_json_select_tracked_person)
+    int32_t id_len = 0;   // the raw text of the "person_id" value in Arena::texts, 0 bytes = no such key
+    int64_t id_off = 0;
 };
 
 struct FileRec {
@@ -60,6 +63,7 @@ struct FileRec {
 struct Arena {
     std::vector<double> values;
     std::vector<Person> persons;
+    std::vector<char> texts;
     std::vector<char> buf;
 };
 
@@ -323,7 +327,7 @@ struct Parser {
     }
     // One element of the "people" array.
     bool person(std::string &key) {
-        Person rec{0, 0, kPersonNoList, 0};
+        Person rec{0, 0, kPersonNoList, 0, 0, 0};
         ws();
         if (p >= end) return fail();
         if (*p != '{') {
@@ -348,6 +352,13 @@ struct Parser {
             ++p;
             if (key == "pose_keypoints_2d") {
                 if (!keypoint_list(rec)) return false;     // a repeated key overrides (dict semantics)
+            } else if (key == "person_id") {
+                ws();
+                const char *first = p;
+                if (!skip(3)) return false;
+                rec.id_off = (int64_t)arena->texts.size();
+                rec.id_len = (int32_t)(p - first);
+                arena->texts.insert(arena->texts.end(), first, p);
             } else if (!skip(3)) {
                 return false;
             }
@@ -403,7 +414,7 @@ struct Parser {
     int32_t document() {
         std::string key;
         people_first = arena->persons.size();
-        const size_t values_first = arena->values.size();
+        const size_t values_first = arena->values.size(), texts_first = arena->texts.size();
         ws();
         bool is_object = false;
         if (p < end && *p == '{') {
@@ -445,7 +456,22 @@ struct Parser {
                 }
             }
         } else {
+            int top = P2S_JSON_DOC_FLOAT;                    // what type(json.load(f)) will be
+            if (p < end) {
+                const char c = *p;
+                if (c == '[') top = P2S_JSON_DOC_LIST;
+                else if (c == '"') top = P2S_JSON_DOC_STRING;
+                else if (c == 't' || c == 'f') top = P2S_JSON_DOC_BOOL;
+                else if (c == 'n') top = P2S_JSON_DOC_NULL;
+            }
+            const char *first = p;
             skip(0);
+            if (ok && top == P2S_JSON_DOC_FLOAT && first < p && *first != 'N' && *first != 'I' && !(*first == '-' && first + 1 < p && first[1] == 'I')) {
+                top = P2S_JSON_DOC_INT;                      // a number without fraction and exponent
+                for (const char *q = first; q < p; ++q)
+                    if (*q == '.' || *q == 'e' || *q == 'E') top = P2S_JSON_DOC_FLOAT;
+            }
+            file_flags |= (int8_t)((top - P2S_JSON_DOC_LIST + 1) << kFileTopShift);
         }
         if (ok) {
             ws();
@@ -454,6 +480,7 @@ struct Parser {
         if (!ok || !is_object || !have_people) {
             arena->persons.resize(people_first);
             arena->values.resize(values_first);
+            arena->texts.resize(texts_first);
             return ok ? P2S_JSON_NO_PEOPLE_LIST : P2S_JSON_UNREADABLE;
         }
         return people_count;
@@ -808,6 +835,32 @@ int p2s_json_gather_largest_person(const p2s_json_batch *b, const int32_t *keypo
                 for (int64_t k = 0; k < (int64_t)n_ids * 3; ++k) dst[k] = nan;   // the except branch: all NaN
         }
     });
+    return P2S_OK;
+}
+
+int p2s_json_person_ids(const p2s_json_batch *b, int64_t *text_off, char *text, int64_t text_capacity, int32_t *file_kind) {
+    if (!b || !text_off) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
+    int64_t at = 0;
+    for (int64_t i = 0; i < b->n_files; ++i) {
+        const FileRec &fr = b->files[(size_t)i];
+        if (file_kind) {
+            const int top = (fr.flags >> kFileTopShift) & 7;
+            file_kind[i] = fr.count >= 0 ? P2S_JSON_DOC_PEOPLE
+                         : fr.count == P2S_JSON_UNREADABLE ? P2S_JSON_DOC_UNREADABLE
+                         : top ? P2S_JSON_DOC_LIST + top - 1
+                         : (fr.flags & kFilePeopleNull) ? P2S_JSON_DOC_PEOPLE_NULL
+                         : (fr.flags & kFilePeopleOther) ? P2S_JSON_DOC_PEOPLE_OTHER : P2S_JSON_DOC_NO_PEOPLE_KEY;
+        }
+        const Arena &arena = b->arenas[(size_t)fr.thread];
+        for (int32_t n = 0; n < fr.count; ++n) {
+            const Person &ps = arena.persons[(size_t)(fr.first_person + n)];
+            text_off[b->person_base[(size_t)i] + n] = at;
+            if (text && at + ps.id_len <= text_capacity) memcpy(text + at, arena.texts.data() + ps.id_off, (size_t)ps.id_len);
+            at += ps.id_len;
+        }
+    }
+    text_off[b->person_base[(size_t)b->n_files]] = at;
+    if (text && at > text_capacity) return p2s_set_error(P2S_ERR_INVALID_ARG, "the texts need %lld bytes, %lld given", (long long)at, (long long)text_capacity);
     return P2S_OK;
 }
 

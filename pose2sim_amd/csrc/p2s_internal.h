@@ -1,8 +1,9 @@
 // What more than one translation unit needs: the device-resident camera, the counter and work-list constants, and what
 // the triangulation entry points (p2s_tri.hip) share with the kernels they drive in other files -- P2sTriArgs, the deep
 // rounds (p2s_tri_deep.hip) and the one-launch kernels (p2s_tri_fused.hip, p2s_tri_pool.hip) -- and P2sOrderArgs, the
-// exact order statistic of p2s_jitter.hip that p2s_confidence.hip launches as well.  Every other argument struct stands
-// in its stage's own .hip file, beside the kernels and the entry points.
+// exact order statistic of p2s_jitter.hip that p2s_confidence.hip and p2s_idswitch.hip launch as well (the latter also
+// the column moments of p2s_confidence.hip).  Every other argument struct stands in its stage's own .hip file, beside the
+// kernels and the entry points.
 #ifndef P2S_INTERNAL_H
 #define P2S_INTERNAL_H
 
@@ -129,7 +130,7 @@ bool p2s_tri_pool_supports(int C, int dtype, int undistort, int lr_swap);
 hipError_t p2s_launch_tri_pool(const P2sTriArgs &a, int dtype, int singles_pct, int tiles_per_wave, hipStream_t s);
 
 // exact order statistics of fp64 columns, NaN skipped (np.nanmedian and its kin): order_stats_kernel of p2s_jitter.hip,
-// which p2s_confidence.hip launches too
+// which p2s_confidence.hip and p2s_idswitch.hip launch too
 struct P2sOrderArgs {
     const double *data;
     const int64_t *col_off;      // [n_cols] first element of every column, or NULL: col * n_rows
@@ -144,5 +145,11 @@ struct P2sOrderArgs {
     int32_t n_cols, n_ranks;
 };
 hipError_t p2s_launch_order_stats(const P2sOrderArgs &a, hipStream_t s);
+
+// conf_compact_kernel and conf_mean_std_kernel of p2s_confidence.hip, which p2s_idswitch.hip launches too: for each of
+// n_cols columns of n_rows entries at cols + col * n_rows, the non-NaN entries in row order -> valid (same layout), their
+// number -> m [n_cols], min and max -> minmax [n_cols][2], np.mean and np.std -> mean_std [n_cols][2] (NaN without entries)
+hipError_t p2s_launch_column_moments(const double *cols, double *valid, int64_t n_rows, int32_t n_cols, int64_t *m, double *minmax,
+                                     double *mean_std, hipStream_t s);
 
 #endif

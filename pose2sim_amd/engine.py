@@ -464,6 +464,79 @@ class Engine:
         _lib.check(fn(self._h, C.byref(ms)))
         return ms.value
 
+    # -- linear_sum_assignment; frame-to-frame person matching (Utilities/id_switch_analyze.py:47-145, 148-291, 364-388) --
+    def lsap(self, cost):
+        """cost: [n][n_rows][n_cols] (or one [n_rows][n_cols]) float64 matrices of one shape, up to 32 x 32.  ->
+        (row_ind, col_ind) [n][min(n_rows, n_cols)] int32 (or one pair of vectors): scipy.optimize.linear_sum_assignment of
+        every matrix, solved on the GPU, exactly scipy's answer with its ties.  A matrix scipy refuses raises scipy's
+        ValueError."""
+        fn = _entry(self._lib, 'p2s_lsap_host')
+        cost = np.ascontiguousarray(cost, dtype=np.float64)
+        single = cost.ndim == 2
+        if single:
+            cost = cost[None]
+        if cost.ndim != 3 or not (1 <= cost.shape[1] <= _lib.P2S_LSAP_MAX and 1 <= cost.shape[2] <= _lib.P2S_LSAP_MAX):
+            raise P2sError(f'cost has shape {cost.shape}; expected [n][1..{_lib.P2S_LSAP_MAX}][1..{_lib.P2S_LSAP_MAX}]')
+        n, k = len(cost), min(cost.shape[1:])
+        rows, cols = np.empty((n, k), dtype=np.int32), np.empty((n, k), dtype=np.int32)
+        status = np.zeros(n, dtype=np.int32)
+        _lib.check(fn(self._h, n, cost.shape[1], cost.shape[2], _optr(cost), _optr(rows), _optr(cols), _optr(status)))
+        if status.any():
+            raise ValueError(_lib.P2S_LSAP_ERRORS[int(status[np.flatnonzero(status)[0]])])
+        return (rows[0], cols[0]) if single else (rows, cols)
+
+    ID_SWITCH_TABLES = ('counts', 'prev', 'zero_run', 'n_matched', 'n_lost', 'n_appeared', 'flags')
+    ID_SWITCH_STATS = ('mean', 'median', 'p95', 'p99', 'min', 'max')
+
+    def id_switch(self, cameras):
+        """cameras: per camera (persons [N][26][3] float64, every listed person of every readable frame in order; offsets
+        [n_frames + 1], the first person of every frame).  -> dict of per-camera lists: the per-frame int32 tables
+        ID_SWITCH_TABLES ('counts' kept persons, 'prev' the last earlier frame with one or -1, 'zero_run' the empty frames
+        between, 'n_matched' / 'n_lost' / 'n_appeared' of the assignment against that frame, 'flags' 0 or why the frame was
+        not matched: 1 / 2 scipy's refusals (_lib.P2S_LSAP_ERRORS), 4 more than 32 kept persons), 'distances' the matched
+        costs in frame and previous-person order, 'kept' the indices of the kept persons in order; and 'stats' [C][6] (ID_SWITCH_STATS; NaN without distances)."""
+        fn = _entry(self._lib, 'p2s_id_switch_host')
+        persons, offsets = [], []
+        for p, o in cameras:
+            p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 26, 3)
+            o = np.ascontiguousarray(o, dtype=np.int64).reshape(-1)
+            if len(o) < 1 or o[0] != 0 or o[-1] != len(p) or (np.diff(o) < 0).any():
+                raise P2sError('offsets must rise from 0 to the number of persons')
+            persons.append(p)
+            offsets.append(o)
+        Cn = len(persons)
+        if Cn < 1:
+            raise P2sError('at least one camera is required')
+        n_frames = np.array([len(o) - 1 for o in offsets], dtype=np.int64)
+        base = np.concatenate([[0], np.cumsum([len(p) for p in persons])])
+        off = np.concatenate([o[:-1] + b for o, b in zip(offsets, base[:-1])] + [base[-1:]]).astype(np.int64)
+        flat = persons[0] if Cn == 1 else np.concatenate(persons)
+        frames, N = int(n_frames.sum()), int(base[-1])
+        tables = np.zeros((len(self.ID_SWITCH_TABLES), frames), dtype=np.int32)
+        dist, n_dist, stats = np.empty(N), np.zeros(Cn, dtype=np.int64), np.empty((Cn, len(self.ID_SWITCH_STATS)))
+        slots = np.zeros(N, dtype=np.int32)
+        _lib.check(fn(self._h, Cn, _ptr(n_frames), _ptr(off), _optr(flat), _optr(tables), _optr(slots), _optr(dist), _ptr(n_dist),
+                      _ptr(stats)))
+        f_off = np.concatenate([[0], np.cumsum(n_frames)])
+        d_off = np.concatenate([[0], np.cumsum(n_dist)])
+        out = {name: [tables[i, f_off[c]:f_off[c + 1]] for c in range(Cn)] for i, name in enumerate(self.ID_SWITCH_TABLES)}
+        out['kept'] = []
+        for c in range(Cn):                                       # the frames' runs of kept persons -> one rising index list
+            counts, first = out['counts'][c].astype(np.int64), offsets[c][:-1]
+            run = np.repeat(first, counts)                        # every kept person's frame's first person
+            nth = np.arange(int(counts.sum())) - np.repeat(np.cumsum(counts) - counts, counts)
+            out['kept'].append(run + slots[base[c] + run + nth])
+        out['distances'] = [dist[d_off[c]:d_off[c + 1]] for c in range(Cn)]
+        out['stats'] = stats
+        return out
+
+    def id_switch_kernel_ms(self):
+        """Kernel time of the last id_switch() call, from HIP events around its kernels."""
+        fn = _entry(self._lib, 'p2s_id_switch_kernel_ms')
+        ms = C.c_float(0)
+        _lib.check(fn(self._h, C.byref(ms)))
+        return ms.value
+
     # -- synchronization (synchronization.py:1271-1343, 1541-1585) -------------------------------------------------------
     def sync_speeds(self, coords, b, a, zi):
         """coords: one [n_frames][n_cols] array per camera, the (x, y) columns of the keypoints to consider with the

@@ -64,6 +64,19 @@ class JsonBatch:
                 _lib.check(self._lib.p2s_json_person_lengths(self._h, _ptr(self._lengths)))
         return self._lengths
 
+    def person_ids(self):
+        """-> (ids, file_kind): ids, per person (file-major), the raw JSON text of its "person_id" value as bytes, None for
+        a person without the key; file_kind [n_files] P2S_JSON_DOC_*: what `counts` does not tell apart about a file without
+        a person list (see p2s_json_person_ids)."""
+        fn = _entry(self._lib, 'p2s_json_person_ids')
+        offsets = np.zeros(int(self.person_base[-1]) + 1, dtype=np.int64)
+        kinds = np.zeros(self.n_files, dtype=np.int32)
+        _lib.check(fn(self._h, _ptr(offsets), None, 0, _ptr(kinds)))
+        text = C.create_string_buffer(max(int(offsets[-1]), 1))
+        _lib.check(fn(self._h, _ptr(offsets), text, int(offsets[-1]), None))
+        raw = text.raw
+        return [raw[a:b] if b > a else None for a, b in zip(offsets[:-1].tolist(), offsets[1:].tolist())], kinds
+
     def gather_keypoints(self, keypoint_ids, max_persons, file_offsets, person_stride, out):
         """out: preallocated float32 / float64 array; see p2s_json_gather_keypoints.  -> n_inexact."""
         ids = np.ascontiguousarray(keypoint_ids, dtype=np.int32)
