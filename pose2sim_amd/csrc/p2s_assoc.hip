@@ -171,7 +171,12 @@ __device__ void jacobi_svd_t(double *A, double *V, int n, int ld, int lane, int 
             for (int i = 0; i < RPL; ++i) { al = fma(x[i], x[i], al); be = fma(y[i], y[i], be); ga = fma(x[i], y[i], ga); }
             group_sum3<L>(al, be, ga);
             // rotate when |ga| > 1e-15 sqrt(al be)  (compared squared: no square root on the test)
-            const bool rot = on && (ga * ga > 1e-30 * (al * be)) && (ga != 0.0);
+            // A column whose squared norm has fallen under 1e-200 is a null column of a rank-deficient matrix (isolated
+            // detections, detections with identical affinities): rounding noise inside the span of the others, so every
+            // sweep takes it off them again and leaves ~1e-16 of it, until (be - al) / (2 ga) squared overflows and the
+            // rotation is NaN.  Its SVT weight is 0 and a rotation with it leaves the other column and V as they are to
+            // the last bit (the matrix entries are O(1)), so it is left alone.
+            const bool rot = on && (ga * ga > 1e-30 * (al * be)) && (ga != 0.0) && (fmin(al, be) > 1e-200);
             // a pair already orthogonal to 1e-7 is orthogonal to ~1e-14 after its rotation (quadratic convergence)
             rotated = rotated || (rot && (ga * ga > 1e-14 * (al * be)));
             if (__any(rot)) {
