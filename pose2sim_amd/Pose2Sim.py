@@ -50,10 +50,13 @@ def _merged(base, override):
 
 
 def _config_dirs(top):
-    """Directories at or below `top` that hold a Config.toml, in os.walk order, each with its first file name (the
-    reference opens `files[0]` of such a directory, Pose2Sim.py:153) and its depth in path components."""
+    """Directories at or below `top` that hold a Config.toml, in os.walk order with the sub-directories taken by name
+    (the reference takes them as the file system lists them, which differs from one machine to the next: a session's
+    trials would run in another order there), each with its first file name (the reference opens `files[0]` of such a
+    directory, Pose2Sim.py:153) and its depth in path components."""
     found = []
-    for root, _dirs, files in os.walk(top):
+    for root, dirs, files in os.walk(top):
+        dirs.sort()                                               # in place: os.walk descends in this order
         if 'Config.toml' in files:
             found.append((root, files[0], len(root.split(os.sep))))
     return found

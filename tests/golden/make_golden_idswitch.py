@@ -17,7 +17,9 @@ count changes 9, 10 and 11 frames apart in the same and in opposite directions; 
 absent; the default and an explicit output folder; a person without the list and a {} entry (KeyError), a 77-number list
 (ValueError), 'people': null (TypeError), a document that is a list (AttributeError), a NaN coordinate on a shared keypoint
 (ValueError from scipy), a camera whose every file is unreadable (ZeroDivisionError), no cam*_json folder and a camera
-folder without files (FileNotFoundError).
+folder without files (FileNotFoundError); a crowd: one camera whose frames rise from 3 to 32 persons and fall again, pairs of
+more than 64 costs and of 32 x 32, about one confidence in ten below 0.1, a person the filter drops listed first among 32
+others, the list reversed from one frame to the next, an empty frame in between.
 
 The file is written with fixed zip time stamps: running this script again reproduces it byte for byte.  It also prints
 the time of the reference's own arithmetic (match_people) per frame at 1, 3 and 8 persons, one CPU core.
@@ -128,6 +130,30 @@ def shared_camera():
     return {f'f{f:03d}.json': document(people) for f, people in enumerate(frames)}
 
 
+CROWD_COUNTS = (3, 8, 9, 12, 0, 20, 20, 32, 32, 32, 31, 13)
+
+
+def crowd_camera():
+    """{file name: text}: CROWD_COUNTS persons a frame, six to a row, walking right; about one confidence in ten is below the
+    threshold.  Frame 8 lists its 32 persons in reverse; frames 6 and 9 list a person with zero confidence first."""
+    rng = np.random.default_rng(40)
+    files = {}
+    for f, n in enumerate(CROWD_COUNTS):
+        people = []
+        for k in range(n):
+            kp = body(150.0 + 300.0 * (k % 6) + 1.5 * f, 200.0 + 150.0 * (k // 6), conf=round(0.5 + 0.01 * k, 2), wobble=rng)
+            kp[rng.random(26) < 0.1, 2] = 0.05
+            people.append(person(kp))
+        if f == 8:
+            people.reverse()
+        if f in (6, 9):
+            ghost = body(900.0, 500.0)
+            ghost[:, 2] = 0.0
+            people.insert(0, person(ghost))
+        files[f'frame_{f:04d}.json'] = document(people)
+    return files
+
+
 def cases():
     """-> list of dicts: name, files {relative path: text}, folders (made even when empty), pose_dir, args."""
     out = []
@@ -176,6 +202,7 @@ def cases():
     add('error_all_unreadable', {'cam01_json': walkers(4, [1] * 4, 28), 'cam02_json': {'a.json': 'x', 'b.json': '{'}}, output_dir='out')
     add('error_no_folders', {'left_json': walkers(3, [1] * 3, 29)}, output_dir='out')
     add('error_no_files', {'cam01_json': walkers(3, [1] * 3, 30), 'cam02_json': {}}, folders=['cam02_json'], output_dir='out')
+    add('crowd', {'cam01_json': crowd_camera()}, output_dir='out')    # last: the cases before it keep their place in the file
     return out
 
 
@@ -298,6 +325,16 @@ def check_claims(out):
                       'error_document_is_a_list': 'AttributeError', 'error_nan_coordinate': 'ValueError', 'error_all_unreadable': 'ZeroDivisionError',
                       'error_no_folders': 'FileNotFoundError', 'error_no_files': 'FileNotFoundError'}, errors
     assert json.loads(str(out['error_nan_coordinate__error']))[1] == 'matrix contains invalid numeric entries'
+    # the crowd: some frame pair has P * Q > 64 and a 32 x 32 pair occurs; every previous or current person finds a partner
+    crowd = result('crowd')['cam01']
+    files = json.loads(str(out['crowd__files']))
+    kept = [sum(any(c > 0 for c in p['pose_keypoints_2d'][2::3]) for p in json.loads(files[name])['people']) for name in sorted(files)]
+    listed = [len(json.loads(files[name])['people']) for name in sorted(files)]
+    assert tuple(kept) == CROWD_COUNTS and max(listed) == 33 and crowd['n_errors'] == 0
+    present = [n for n in kept if n > 0]
+    pairs = list(zip(present, present[1:]))
+    assert any(p * q > 64 for p, q in pairs) and (32, 32) in pairs and max(p * q for p, q in pairs) == 1024
+    assert len(crowd['match_distances']) == sum(min(p, q) for p, q in pairs) and max(crowd['match_distances']) < 1e9
 
 
 if __name__ == '__main__':

@@ -24,6 +24,8 @@ SHORT_RUN = np.array([[1.0], [2.0], [3.0], [np.nan], [np.nan], [np.nan], [np.nan
 INF_RUN = np.array([[1.0], [2.0], [np.inf], [4.0], [5.0], [6.0]])
 OUT = np.empty(64)                                                  # room for any output of the cases below
 IOUT = np.empty(64, dtype=np.int64)
+IDS_OUT = (P(IOUT), P(IOUT), P(OUT), P(IOUT), P(OUT))                # tables, kept, distances, n_distances, stats
+CONF_OUT = (P(OUT), P(IOUT), P(IOUT), P(IOUT))                      # stats, counts, below, bands
 
 # (entry point, arguments after the context, return code, message)
 CASES = [
@@ -57,6 +59,37 @@ CASES = [
     ('p2s_jitter_host', (0, P(i8(3)), P(f8(3, 26, 3)), 5.0, 1920.0, 1080.0) + (None,) * 7 + (0, None, None), INVALID, 'n_cams=0 outside [1, 65535]'),
     ('p2s_jitter_host', (1, P(i8(0)), P(f8(3, 26, 3)), 5.0, 1920.0, 1080.0) + (None,) * 7 + (0, None, None), INVALID,
      'camera 0 has 0 frames; expected 1 .. 2^31 - 1'),
+    # p2s_id_switch_host(n_cams, n_frames, person_off, persons, tables, kept, distances, n_distances, stats)
+    ('p2s_id_switch_host', (0, P(i8(1)), P(i8(0, 1)), P(f8(1, 26, 3))) + IDS_OUT, INVALID, 'n_cams=0 outside [1, 65535]'),
+    ('p2s_id_switch_host', (65536, P(i8(1)), P(i8(0, 1)), P(f8(1, 26, 3))) + IDS_OUT, INVALID, 'n_cams=65536 outside [1, 65535]'),
+    ('p2s_id_switch_host', (1, None, P(i8(0, 1)), P(f8(1, 26, 3))) + IDS_OUT, INVALID, 'null argument'),
+    ('p2s_id_switch_host', (1, P(i8(1)), None, P(f8(1, 26, 3))) + IDS_OUT, INVALID, 'null argument'),
+    ('p2s_id_switch_host', (1, P(i8(-1)), P(i8(0, 1)), P(f8(1, 26, 3))) + IDS_OUT, INVALID, 'camera 0 has -1 frames; expected 0 .. 2^31 - 1'),
+    ('p2s_id_switch_host', (2, P(i8(1, 2 ** 31)), P(i8(0, 1)), P(f8(1, 26, 3))) + IDS_OUT, INVALID,
+     'camera 1 has 2147483648 frames; expected 0 .. 2^31 - 1'),
+    ('p2s_id_switch_host', (2, P(i8(2 ** 31 - 1, 1)), P(i8(0, 1)), P(f8(1, 26, 3))) + IDS_OUT, INVALID, '2147483648 frames are too many'),
+    ('p2s_id_switch_host', (1, P(i8(1)), P(i8(1, 2)), P(f8(2, 26, 3))) + IDS_OUT, INVALID, 'person_off must start at 0'),
+    ('p2s_id_switch_host', (1, P(i8(2)), P(i8(0, 2, 1)), P(f8(2, 26, 3))) + IDS_OUT, INVALID, 'person_off must not decrease (frame 1)'),
+    ('p2s_id_switch_host', (1, P(i8(1)), P(i8(0, 2 ** 31)), P(f8(1, 26, 3))) + IDS_OUT, INVALID, '2147483648 persons are too many'),
+    ('p2s_id_switch_host', (1, P(i8(1)), P(i8(0, 1)), None) + IDS_OUT, INVALID, 'null argument'),
+    # p2s_confidence_stats_host(n_cams, n_frames, n_kpts, tables, n_thresholds, thresholds, stats, counts, below, bands)
+    ('p2s_confidence_stats_host', (0, P(i8(2)), 3, P(f8(2, 3)), 1, P(f8(1))) + CONF_OUT, INVALID, 'n_cams=0 outside [1, 65535]'),
+    ('p2s_confidence_stats_host', (1, P(i8(2)), 0, P(f8(2, 3)), 1, P(f8(1))) + CONF_OUT, INVALID, 'n_kpts=0 outside [1, 64]'),
+    ('p2s_confidence_stats_host', (1, P(i8(2)), 65, P(f8(2, 65)), 1, P(f8(1))) + CONF_OUT, INVALID, 'n_kpts=65 outside [1, 64]'),
+    ('p2s_confidence_stats_host', (1, P(i8(2)), 3, P(f8(2, 3)), -1, P(f8(1))) + CONF_OUT, INVALID, 'n_thresholds=-1 outside [0, 8]'),
+    ('p2s_confidence_stats_host', (1, P(i8(2)), 3, P(f8(2, 3)), 9, P(f8(9))) + CONF_OUT, INVALID, 'n_thresholds=9 outside [0, 8]'),
+    ('p2s_confidence_stats_host', (1, None, 3, P(f8(2, 3)), 1, P(f8(1))) + CONF_OUT, INVALID, 'null argument'),
+    ('p2s_confidence_stats_host', (1, P(i8(2)), 3, None, 1, P(f8(1))) + CONF_OUT, INVALID, 'null argument'),
+    ('p2s_confidence_stats_host', (1, P(i8(2)), 3, P(f8(2, 3)), 1, None) + CONF_OUT, INVALID, 'null argument'),
+    ('p2s_confidence_stats_host', (2, P(i8(2, 0)), 3, P(f8(2, 3)), 1, P(f8(1))) + CONF_OUT, INVALID, 'camera 1 has 0 frames; expected 1 .. 2^31 - 1'),
+    ('p2s_confidence_stats_host', (1, P(i8(2 ** 31)), 3, P(f8(2, 3)), 1, P(f8(1))) + CONF_OUT, INVALID,
+     'camera 0 has 2147483648 frames; expected 1 .. 2^31 - 1'),
+    ('p2s_confidence_stats_host', (5, P(i8(*[2 ** 31 - 1] * 5)), 1, P(f8(2, 1)), 0, None) + CONF_OUT, INVALID, '10737418235 frames are too many'),
+    # p2s_column_mean_std_host(n_rows, n_cols, data, mean, std, counts)
+    ('p2s_column_mean_std_host', (-1, 2, P(f8(2, 4)), P(OUT), P(OUT), P(IOUT)), INVALID, 'bad shape: -1 rows, 2 columns'),
+    ('p2s_column_mean_std_host', (2 ** 31, 2, P(f8(2, 4)), P(OUT), P(OUT), P(IOUT)), INVALID, 'bad shape: 2147483648 rows, 2 columns'),
+    ('p2s_column_mean_std_host', (4, -1, P(f8(2, 4)), P(OUT), P(OUT), P(IOUT)), INVALID, 'bad shape: 4 rows, -1 columns'),
+    ('p2s_column_mean_std_host', (4, 2, None, P(OUT), P(OUT), P(IOUT)), INVALID, 'null argument'),
 ]
 KEEP = [B, A, ZI, A_BAD, NAN_DATA, SHORT_RUN, INF_RUN, OUT, IOUT]    # the temporaries above are kept alive by ctypes' own references
 
@@ -88,22 +121,50 @@ def test_null_context_is_refused(lib, name):
     assert lib.p2s_last_error().decode() == 'null context'
 
 
+def test_lsap_refuses_a_bad_shape(lib, ctx):
+    """p2s_lsap_host solves on the host without a context, by design: its refusals are the same with and without one."""
+    cost, out = f8(1, 33, 33), np.empty(64, dtype=np.int32)
+    for h in (ctx, None):
+        for n, n_rows, n_cols in ((1, 33, 2), (1, 2, 33), (1, 0, 2), (1, 2, 0), (-1, 2, 2), (2 ** 31, 2, 2)):
+            assert lib.p2s_lsap_host(h, n, n_rows, n_cols, P(cost), P(out), P(out), P(out)) == INVALID
+            assert lib.p2s_last_error().decode() == f'bad shape: {n} matrices of {n_rows} x {n_cols}; expected 1 .. 32 rows and columns'
+        for args in ((None, P(out), P(out), P(out)), (P(cost), None, P(out), P(out)), (P(cost), P(out), None, P(out)), (P(cost), P(out), P(out), None)):
+            assert lib.p2s_lsap_host(h, 1, 2, 2, *args) == INVALID and lib.p2s_last_error().decode() == 'null argument'
+        assert lib.p2s_lsap_host(h, 0, 2, 2, None, None, None, None) == 0                # no matrix: nothing to do
+
+
 def test_kernel_times_refuse_until_their_own_stage_has_run(lib):
-    """The two stages that time their kernels share one pair of events; each query still answers for its own stage."""
+    """The four stages that time their kernels share one pair of events; each query still answers for its own stage."""
     from pose2sim_amd.engine import Engine
-    ms = C.c_float(0)
-    for name in ('p2s_reproject_kernel_ms', 'p2s_jitter_kernel_ms'):
-        assert getattr(lib, name)(None, C.byref(ms)) == INVALID and lib.p2s_last_error().decode() == 'null argument'
-    eng = Engine(0)
-    assert lib.p2s_reproject_kernel_ms(eng._h, C.byref(ms)) == INVALID
-    assert lib.p2s_last_error().decode() == 'p2s_reproject_host has not run on this context'
-    assert lib.p2s_jitter_kernel_ms(eng._h, C.byref(ms)) == INVALID
-    assert lib.p2s_last_error().decode() == 'p2s_jitter_host has not run on this context'
     P34 = np.array([[[1000.0, 0, 960, 0], [0, 1000.0, 540, 0], [0, 0, 1, 4.0]]])
-    eng.reproject(np.zeros((3, 2, 3)), P=P34, sizes=np.array([[1920.0, 1080.0]]))
-    assert eng.reproject_kernel_ms() >= 0.0
-    assert lib.p2s_jitter_kernel_ms(eng._h, C.byref(ms)) == INVALID                  # another stage's call does not count
-    assert lib.p2s_last_error().decode() == 'p2s_jitter_host has not run on this context'
-    eng.jitter([np.ones((4, 26, 3))])
-    assert eng.jitter_kernel_ms() >= 0.0 and eng.reproject_kernel_ms() >= 0.0
-    eng.close()
+    # (the query, the entry point its refusal names, a small call of that stage)
+    stages = (('p2s_reproject_kernel_ms', 'p2s_reproject_host', lambda e: e.reproject(np.zeros((3, 2, 3)), P=P34, sizes=np.array([[1920.0, 1080.0]]))),
+              ('p2s_jitter_kernel_ms', 'p2s_jitter_host', lambda e: e.jitter([np.ones((4, 26, 3))])),
+              ('p2s_confidence_kernel_ms', 'p2s_confidence_stats_host', lambda e: e.confidence_stats([np.full((4, 26), 0.5)])),
+              ('p2s_id_switch_kernel_ms', 'p2s_id_switch_host', lambda e: e.id_switch([(np.full((2, 26, 3), 0.5), [0, 1, 2])])))
+    ms = C.c_float(0)
+    for query, _, _ in stages:
+        assert getattr(lib, query)(None, C.byref(ms)) == INVALID and lib.p2s_last_error().decode() == 'null argument'
+
+    def refuses(eng, query, entry):
+        return getattr(lib, query)(eng._h, C.byref(ms)) == INVALID and lib.p2s_last_error().decode() == f'{entry} has not run on this context'
+
+    def answers(eng, query):
+        ms.value = -1.0
+        return getattr(lib, query)(eng._h, C.byref(ms)) == 0 and ms.value >= 0.0
+
+    for first in range(len(stages)):                                 # every stage as the first one of a fresh context
+        eng = Engine(0)
+        assert all(refuses(eng, query, entry) for query, entry, _ in stages)
+        stages[first][2](eng)
+        assert answers(eng, stages[first][0])
+        for query, entry, _ in stages:                               # another stage's call does not count
+            assert query == stages[first][0] or refuses(eng, query, entry), (stages[first][0], query)
+        for n, (_, _, run) in enumerate(stages):                     # the others one by one: what has run answers, the rest refuses
+            if n != first:
+                run(eng)
+            done = set(range(n + 1)) | {first}
+            for k, (query, entry, _) in enumerate(stages):
+                assert answers(eng, query) if k in done else refuses(eng, query, entry), (first, n, query)
+        assert all(answers(eng, query) for query, _, _ in stages)
+        eng.close()

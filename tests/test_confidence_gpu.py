@@ -90,6 +90,26 @@ def test_empty_and_single_row_tables(engine):
         assert same(ref[key], res[key]), key
 
 
+@pytest.mark.parametrize('K', (1, 2, 25, 63, 64))
+def test_tables_of_other_widths_equal_the_stand_in(engine, K, capsys):
+    """Cameras of 1, 65 and 4097 frames, no multiple of the transposition's 64-frame tile, at widths on the edges of its
+    [64][65] LDS tile; three-decimal values, about one entry in ten NaN, at other frames in every column."""
+    rng = np.random.default_rng(K)
+    tables = [np.round(rng.uniform(0.0, 1.0, (F, K)), 3) for F in (1, 65, 4097)]
+    for t in tables:
+        t[rng.random(t.shape) < 0.1] = np.nan
+    tables[0][0, 0] = 0.4                                             # the one-frame camera keeps an entry, on a band's edge
+    ths = (0.4, 0.6)
+    ref = cn.NumpyConfidenceEngine().confidence_stats(tables, ths)
+    res = engine.confidence_stats(tables, ths)
+    with capsys.disabled():
+        print(f'confidence_stats K = {K}, frames (1, 65, 4097): entries {res["counts"].sum(axis=1).tolist()} (NumPy {ref["counts"].sum(axis=1).tolist()}), '
+              f'mean of the last column {res["stats"][:, -1, 0].tolist()} (NumPy {ref["stats"][:, -1, 0].tolist()})')
+    assert (ref['counts'][1:] > 0).all() and (ref['counts'][1:] < np.array([65, 4097])[:, None]).all()     # every long column has NaN to skip
+    for key in ref:
+        assert res[key].dtype == ref[key].dtype and same(ref[key], res[key]), key
+
+
 def test_refusals(engine):
     from pose2sim_amd._lib import P2sError
     for tables, ths, text in (([np.zeros((2, 65))], (0.4,), r'n_kpts=65 outside \[1, 64\]'),

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 from scipy import signal
 
+import idswitch_numpy as isn
 from pose2sim_amd import skeletons, synth
 
 pytestmark = pytest.mark.gpu
@@ -60,12 +61,25 @@ def stages(size):
     stats_in = clean.copy()
     stats_in[rng.random(clean.shape) < 0.1] = np.nan
     series = [col['xyl'][:Fc - 2 * c, 0, c].astype(np.float64) for c in range(2)]     # [frames][26][3]
+    conf_tables = [rng.uniform(0.0, 1.0, (n, K)) for n in (Fc, Fc - 7)]
+    for t in conf_tables:
+        t[rng.random(len(t)) < 0.1] = np.nan                           # frames without a person
+    costs = rng.uniform(0.0, 100.0, (Fc, 7, 5))
+    crowds = [isn.seeded_camera(Fc, 9000 + c, max_persons=9) for c in range(2)]
     prm = Engine.tri_params(15.0, 0.3, 2)
     prm_swap = Engine.tri_params(15.0, 0.3, 2, lr_swap=True)
 
     def jitter(e):
         out = e.jitter(series, multiplier=2.0)
         return tuple(np.asarray(v) for k in sorted(out) for v in (out[k] if isinstance(out[k], list) else [out[k]]))
+
+    def confidence_stats(e):
+        out = e.confidence_stats(conf_tables, (0.4, 0.6))
+        return tuple(out[k] for k in ('stats', 'counts', 'below', 'below_rate', 'bands', 'band_rate'))
+
+    def id_switch(e):
+        out = e.id_switch(crowds)
+        return tuple(np.asarray(v) for k in isn.TABLES + ('distances', 'kept') for v in out[k]) + (out['stats'],)
 
     return [
         ('triangulate', lambda e: e.triangulate(xyl, prm)),
@@ -85,6 +99,10 @@ def stages(size):
         ('reproject_distorted', lambda e: e.reproject(Qn, cal=dcams, sizes=sizes, raw=True)),
         ('column_order_stats', lambda e: e.column_order_stats(stats_in, [0, -1, Fc // 2, Fc])),
         ('jitter', jitter),
+        ('confidence_stats', confidence_stats),
+        ('column_mean_std', lambda e: e.column_mean_std(stats_in)),
+        ('lsap', lambda e: e.lsap(costs)),
+        ('id_switch', id_switch),
     ]
 
 

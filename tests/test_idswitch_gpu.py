@@ -1,7 +1,9 @@
 """The ID switch kernels, the assignment solver and the whole utility on the MI355X, through the C-ABI: against the goldens
 recorded from the reference (tests/golden/idswitch_units.npz), against NumPy and scipy themselves on single pairs and on
-seeded matrices, and against the NumPy / scipy stand-in on scans of every length around the tile sizes and on large seeded
-tables.  There is no tolerance: every array must be equal.  Every test prints its figures before it asserts."""
+seeded matrices, and against the NumPy / scipy stand-in on scans of every length around the tile sizes, on large seeded
+tables and on crowded frames: up to 32 x 32 persons, pair counts around the 64 lanes of a round and up to sixteen rounds, pairs that cannot
+match, matrices scipy refuses and exact ties.  There is no tolerance: every array must be equal.  Every test prints its
+figures before it asserts."""
 import json
 import os
 import time
@@ -189,3 +191,177 @@ def test_large_seeded_tables_equal_the_stand_in(engine, C, F, seed, capsys):
     for key in ref:
         for a, b in zip(first[key], res[key]):
             assert np.asarray(a).tobytes() == np.asarray(b).tobytes(), key     # two runs, the same bytes
+
+
+# ---- crowded frames: the match kernel beyond one round of 64 pairs, up to 32 x 32 persons ------------------------------------
+CROWDS = (8, 9, 12, 20, 32)                                          # max_persons of the seeded crowd cameras
+BOUNDARY_COUNTS = (7, 9, 0, 8, 8, 5, 13, 5, 0, 0, 16, 8, 1, 32, 1, 32, 32, 31, 32, 20, 32, 33, 32, 32)   # kept persons per frame
+# P * Q of every matched frame of BOUNDARY_COUNTS, against the last non-empty frame; the two frames that touch the 33 are refused
+BOUNDARY_PAIRS = (63, 72, 64, 40, 65, 65, 80, 128, 8, 32, 32, 32, 1024, 992, 992, 640, 640, 1024)
+
+
+def pair_counts(tables, c=0):
+    """P * Q of every frame of camera c that has persons and a previous frame, 0 elsewhere, from the stand-in's tables."""
+    counts, prev = tables['counts'][c].astype(np.int64), tables['prev'][c]
+    return np.where((counts > 0) & (prev >= 0), counts[np.maximum(prev, 0)] * counts, 0)
+
+
+def ghost_frames(cam, tables, c=0):
+    """Frames that list another number of persons than the filter keeps."""
+    return int((np.diff(cam[1]) != tables['counts'][c]).sum())
+
+
+@pytest.fixture(scope='module')
+def crowds():
+    """{max_persons: (camera, the stand-in's result on it alone)}; the fixture proves what the tests below lean on."""
+    out = {}
+    for m in CROWDS:
+        cam = isn.seeded_camera(400, 7000 + m, max_persons=m)
+        ref = isn.NumpyIdSwitchEngine().id_switch([cam])
+        pq = pair_counts(ref)
+        assert pq.max() == 64 and (pq == 64).any() if m == 8 else (pq > 64).any(), m     # exactly one full round, or more
+        assert ghost_frames(cam, ref) > 0 and ref['n_lost'][0].sum() > 0 and ref['n_appeared'][0].sum() > 0 and not ref['flags'][0].any(), m
+        out[m] = (cam, ref)
+    return out
+
+
+@pytest.mark.parametrize('max_persons', CROWDS)
+def test_seeded_crowd_equals_the_stand_in(engine, crowds, max_persons, capsys):
+    cam, ref = crowds[max_persons]
+    pq = pair_counts(ref)
+    with capsys.disabled():
+        print(f'crowd of {max_persons}: {int((pq > 64).sum())} frames with P*Q > 64, max P*Q {int(pq.max())}, '
+              f'{ghost_frames(cam, ref)} ghost frames, {len(ref["distances"][0])} distances')
+    same_tables(engine.id_switch([cam]), ref)
+
+
+def test_seeded_crowds_in_one_call_equal_the_stand_in(engine, crowds, capsys):
+    """Cameras of very different person totals: n_rows is the largest one's, the smaller cameras' columns end in NaN."""
+    cams = [crowds[m][0] for m in CROWDS]
+    ref = {key: [crowds[m][1][key][0] for m in CROWDS] for key in isn.TABLES + ('distances', 'kept')}
+    ref['stats'] = np.concatenate([crowds[m][1]['stats'] for m in CROWDS])
+    persons = [len(p) for p, _ in cams]
+    with capsys.disabled():
+        print(f'crowds {CROWDS} in one call: {persons} persons, {[len(d) for d in ref["distances"]]} distances')
+    assert max(persons) > 2 * min(persons) and all(len(d) < max(persons) for d in ref['distances'])
+    same_tables(engine.id_switch(cams), ref)
+
+
+def boundary_camera(digits):
+    """BOUNDARY_COUNTS persons a frame out of a pool of 33: everyone has a home, drifts a little from frame to frame, has
+    about one confidence in ten below 0.1 and stands at a seeded random place of the frame's list."""
+    rng = np.random.default_rng(33)
+    home = np.stack([150.0 + 210.0 * (np.arange(33) % 8), 150.0 + 190.0 * (np.arange(33) // 8)], axis=1)     # [33][2]
+    shape = rng.uniform(-60, 60, (33, 26, 2))
+    persons = []
+    for f, n in enumerate(BOUNDARY_COUNTS):
+        who = rng.permutation(33)[:n]                                  # who is there, in list order
+        xy = home[who, None, :] + shape[who] + rng.normal(0, 2.0, (n, 26, 2))
+        conf = rng.uniform(0.3, 0.98, (n, 26))
+        conf[rng.random(conf.shape) < 0.1] = 0.05
+        persons.append(np.concatenate([xy, conf[..., None]], axis=2))
+    persons = np.concatenate(persons)
+    return (persons if digits is None else np.round(persons, digits)), np.concatenate([[0], np.cumsum(BOUNDARY_COUNTS)]).astype(np.int64)
+
+
+@pytest.mark.parametrize('digits', (3, None), ids=('three decimals', 'full precision'))
+def test_pair_count_boundaries(engine, digits, capsys):
+    """One pair short of a round, a round, one pair more, two rounds, sixteen, and back; across empty frames; next to a
+    frame with too many persons."""
+    cam = boundary_camera(digits)
+    ref = isn.NumpyIdSwitchEngine().id_switch([cam])
+    pq, flags = pair_counts(ref), ref['flags'][0]
+    with capsys.disabled():
+        print(f'pair counts per frame {pq.tolist()}, flags {flags.tolist()}, matched {ref["n_matched"][0].tolist()}')
+    assert tuple(ref['counts'][0]) == BOUNDARY_COUNTS
+    assert tuple(pq[(pq > 0) & (flags == 0)]) == BOUNDARY_PAIRS
+    assert flags.tolist() == [4 if f in (21, 22) else 0 for f in range(len(BOUNDARY_COUNTS))]
+    assert (ref['n_matched'][0][(pq > 0) & (flags == 0)] > 0).all()
+    same_tables(engine.id_switch([cam]), ref)
+
+
+def half_bodies(n, k, seed):
+    """Two frames of n persons: k with keypoints 0..12 only, then k with keypoints 13..25 only, and n - k whole ones in
+    both, everyone at a seeded place of the list.  Upper against lower body shares no keypoint: 1e9."""
+    rng = np.random.default_rng(seed)
+    home = rng.uniform([200, 200], [1700, 900], (n, 2))
+    shape = rng.uniform(-60, 60, (26, 2))
+    frames = []
+    for keep in (np.arange(26) < 13, np.arange(26) >= 13):
+        xy = home[:, None, :] + shape[None] + rng.normal(0, 2.0, (n, 26, 2))
+        conf = rng.uniform(0.3, 0.98, (n, 26))
+        conf[:k] = np.where(keep, conf[:k], 0.05)
+        frames.append(np.round(np.concatenate([xy, conf[..., None]], axis=2), 3)[rng.permutation(n)])
+    return np.concatenate(frames), [0, n, 2 * n]
+
+
+def test_unmatchable_pairs_inside_a_crowd(engine, capsys):
+    cams = [half_bodies(16, 12, 1), half_bodies(32, 28, 2)]
+    ref = isn.NumpyIdSwitchEngine().id_switch(cams)
+    figures = [tuple(int(ref[key][c][1]) for key in ('n_matched', 'n_lost', 'n_appeared')) for c in range(2)]
+    with capsys.disabled():
+        print(f'half bodies among 16 and 32 persons: (matched, lost, appeared) {figures}')
+    assert all(min(f) > 0 for f in figures) and not any(fl.any() for fl in ref['flags'])
+    same_tables(engine.id_switch(cams), ref)
+
+
+def refused_camera():
+    """Five frames of 12 persons: a NaN coordinate on a shared keypoint of the last person of frame 1 (a cost that is NaN
+    at pair 64 and beyond), an infinite person at the end of frame 3."""
+    rng = np.random.default_rng(12)
+    home = rng.uniform([200, 200], [1700, 900], (12, 2))
+    shape = rng.uniform(-60, 60, (26, 2))
+    xy = home[None, :, None, :] + shape[None, None] + rng.normal(0, 2.0, (5, 12, 26, 2))
+    conf = rng.uniform(0.3, 0.98, (5, 12, 26))
+    conf[rng.random(conf.shape) < 0.1] = 0.05
+    p = np.round(np.concatenate([xy, conf[..., None]], axis=3), 3)
+    p[0, :, 25, 2] = 0.9
+    p[1, 11, 25] = [np.nan, p[1, 11, 25, 1], 0.9]
+    p[3, 11, :, 0], p[3, 11, :, 2] = np.inf, 0.9
+    return p.reshape(60, 26, 3), 12 * np.arange(6)
+
+
+def test_scipys_refusals_on_a_large_matrix(engine, capsys):
+    cam = refused_camera()
+    ref = isn.NumpyIdSwitchEngine().id_switch([cam])
+    with capsys.disabled():
+        print(f'refusals at 12 x 12: flags {ref["flags"][0].tolist()}, matched {ref["n_matched"][0].tolist()}')
+    assert ref['flags'][0].tolist() == [0, 1, 1, 2, 2] and not ref['n_matched'][0].any() and len(ref['distances'][0]) == 0
+    first = np.array([isn.pair_cost(a, cam[0][12 + 11]) for a in cam[0][:12]])       # the column of frame 1's last person
+    assert np.isnan(first).all() and 5 * 12 + 11 >= 64
+    res = engine.id_switch([cam])
+    same_tables(res, ref)
+    assert np.isnan(res['stats']).all()
+
+
+def twins_camera(n, seed):
+    """Three frames of n persons, three of them listed twice with the same 78 numbers: equal rows and equal columns in the
+    cost matrix; the twins stand still from frame 0 to 1 (a block of exact zeros) and move together from 1 to 2."""
+    rng = np.random.default_rng(seed)
+    home = rng.uniform([200, 200], [1700, 900], (n - 3, 2))
+    shape = rng.uniform(-60, 60, (26, 2))
+    frames = []
+    for f in range(3):
+        xy = home[:, None, :] + shape[None] + rng.normal(0, 2.0, (n - 3, 26, 2))
+        conf = rng.uniform(0.3, 0.98, (n - 3, 26))
+        conf[rng.random(conf.shape) < 0.1] = 0.05
+        p = np.round(np.concatenate([xy, conf[..., None]], axis=2), 3)
+        if f == 1:
+            p[:3] = frames[0][:3]                                     # list places 0..2 of frame 0 hold the first twins
+        frames.append(np.concatenate([p, p[:3]]))
+    order = [np.arange(n), rng.permutation(n), rng.permutation(n)]
+    return np.concatenate([fr[o] for fr, o in zip(frames, order)]), [0, n, 2 * n, 3 * n]
+
+
+def test_exact_ties_inside_a_crowd(engine, capsys):
+    cams = [twins_camera(n, n) for n in (20, 32, 9)]
+    ref = isn.NumpyIdSwitchEngine().id_switch(cams)
+    with capsys.disabled():
+        print(f'twins among 20, 32 and 9 persons: matched {[m.tolist() for m in ref["n_matched"]]}, '
+              f'zero distances {[int((d == 0).sum()) for d in ref["distances"]]}')
+    for c, (p, off) in enumerate(cams):
+        for f in range(3):
+            rows = p[off[f]:off[f + 1]].reshape(-1, 78)
+            assert len(rows) - len(np.unique(rows, axis=0)) == 3, (c, f)              # three persons twice
+        assert (ref['distances'][c] == 0).sum() == 6 and not ref['flags'][c].any()    # both twins of each, matched at cost 0
+    same_tables(engine.id_switch(cams), ref)

@@ -19,11 +19,12 @@ from test_jitter_host import same
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'idswitch_units.npz')
 ALL = json.loads(str(np.load(GOLDEN)['cases']))
 ERROR_CASES = [n for n in ALL if n.startswith('error_')]
-assert len(ALL) == 13 and len(ERROR_CASES) == 9
+assert len(ALL) == 14 and len(ERROR_CASES) == 9
 ERRORS = {e.__name__: e for e in (KeyError, ValueError, TypeError, AttributeError, ZeroDivisionError, FileNotFoundError)}
 RESULT_KEYS = ['events', 'match_distances', 'detection_counts', 'person_id_values', 'n_frames', 'n_errors', 'distance_stats', 'pattern_counts']
-# every shape from 1 x 1 to 8 x 8, and the large and the lopsided ones
+# every shape from 1 x 1 to 8 x 8, the large and the lopsided ones, and sizes between: around 8 and 16, nearly square both ways
 SHAPES = [(r, c) for r in range(1, 9) for c in range(1, 9)] + [(32, 32), (1, 32), (32, 1), (32, 20), (20, 32)]
+SHAPES += [(8, 9), (9, 8), (9, 9), (13, 17), (17, 13), (16, 16), (31, 32), (32, 31)]
 KINDS = ('continuous', 'integers 0 to 2', 'continuous, 40 % at 1e9', 'integers, 40 % at 1e9', 'all 1e9')
 
 

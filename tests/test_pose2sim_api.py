@@ -53,6 +53,24 @@ def test_config_discovery_matches_reference(golden_dir, tmp_path, monkeypatch):
         Pose2Sim.read_config_files(str(tmp_path / 'nowhere'))
 
 
+def test_trials_come_in_name_order_whatever_the_file_system_lists(tmp_path, monkeypatch):
+    """A directory listing has no defined order; the session's trials must not depend on it."""
+    root = str(tmp_path / 'session')
+    for name in ('', 'b_trial', 'a_trial', 'c_trial'):
+        os.makedirs(os.path.join(root, name), exist_ok=True)
+        open(os.path.join(root, name, 'Config.toml'), 'w').write("[project]\nexclude_from_batch = []\n")
+    walk = os.walk
+
+    def listed_backwards(top):
+        for where, dirs, files in walk(top):
+            dirs.sort(reverse=True)                                   # the same list: what the caller does to it still counts
+            yield where, dirs, files
+    monkeypatch.setattr(Pose2Sim.os, 'walk', listed_backwards)
+    monkeypatch.chdir(str(tmp_path))
+    level, dicts = Pose2Sim.read_config_files(root)
+    assert level == 2 and [os.path.basename(d['project']['project_dir']) for d in dicts] == ['a_trial', 'b_trial', 'c_trial']
+
+
 def test_batch_session_runs_every_trial_but_the_excluded_one(tmp_path, monkeypatch):
     ids, names, swap = skeletons.keypoints('HALPE_26')
     root = str(tmp_path / 'session')
