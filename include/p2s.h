@@ -218,6 +218,21 @@ int p2s_filter_columns_host(p2s_ctx *ctx, int32_t kind, int64_t n_frames, int32_
 #define P2S_ERR_GCV_SINGULAR (-9)      /* a zero pivot in the banded LU solve: "singular matrix"                    */
 int p2s_gcv_spline_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const double *data, int32_t auto_mode,
                         double lam, double smoothing_factor, double *out, double *lam_out);
+/* loess_filter_1d (filtering.py:532-558) on every column of a row-major [n_frames][n_cols] float64 matrix: every run of at
+ * least min_run consecutive samples that are not NaN (zeros are data) is replaced by its local linear regression,
+ * statsmodels' lowess(run, frame_indices, frac = k / len, it = 0, delta = 0): at sample i the weighted least-squares line
+ * through the k run samples nearest to i -- the block [l, l + k) of the run with l = i - k / 2 clamped to the run --
+ * evaluated at i, with the tricube weights (1 - (|j - i| / h)^3)^3, h = max(i - l, l + k - 1 - i).  A sample at distance h
+ * weighs exactly 0, so the result does not depend on which of two equally distant neighbours is kept; a fit with one
+ * non-zero weight (k = 2) returns the sample.  Other samples are copied.  The caller derives k and min_run from the
+ * reference's nb_values_used: k = int(nb + 1e-10), min_run = floor(nb) + 1.  statsmodels is not importable where this
+ * was built and has never run here: restated from its published algorithm, checked against goldens recorded through
+ * the reference's own loess_filter_1d with a stand-in for lowess and against a multiprecision solve of the definition.
+ * Refused with P2S_ERR_INVALID_ARG: k outside 2..8191, min_run <= k, and any infinity in the data (what statsmodels
+ * answers for one has not been recorded); all of it is checked before anything is copied or launched, and on such a
+ * refusal `out` is untouched.  An empty shape is P2S_OK.  HOST pointers; blocks. */
+int p2s_loess_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const double *data, int32_t k, int64_t min_run,
+                   double *out);
 /* trc_evaluate's per-frame quantities and sums (Utilities/trc_evaluate.py:114-238) for xyz [n_frames][n_markers][3]:
  *   bones      [n_bones][2] int32  (parent, child) marker indices
  *   bone_len   [n_bones][n_frames]      |child - parent|, 0 -> NaN             (compute_bone_lengths :135-139)

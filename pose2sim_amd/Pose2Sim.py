@@ -156,8 +156,8 @@ def triangulation(config=None):
 
 def filtering(config=None):
     """Filtering of the .trc files (filtering.filter_all): every filter type of the reference's filter_mapping --
-    butterworth, butterworth_on_speed, gaussian, median, one_euro, kalman and gcv_spline -- except loess, which is
-    refused with NotImplementedError."""
+    butterworth, butterworth_on_speed, gaussian, median, one_euro, kalman, gcv_spline and loess (the last
+    parity-unpinned against statsmodels, which has never run where this was built: filtering.loess_filter)."""
     _run_stage('filtering', config)
 
 

@@ -83,6 +83,7 @@ SIGNATURES = {
     'p2s_butterworth_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'p2s_filter_columns_host': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     'p2s_gcv_spline_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    'p2s_loess_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
     'p2s_sync_speeds_host': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     'p2s_lagged_pearson_host': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
@@ -133,7 +134,7 @@ OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_h
             'p2s_copy_files', 'p2s_reproject_host', 'p2s_reproject_kernel_ms', 'p2s_write_openpose_files',
             'p2s_column_order_stats_host', 'p2s_jitter_host', 'p2s_jitter_kernel_ms', 'p2s_json_select_tracked_person',
             'p2s_column_mean_std_host', 'p2s_confidence_stats_host', 'p2s_confidence_kernel_ms', 'p2s_lsap_host',
-            'p2s_id_switch_host', 'p2s_id_switch_kernel_ms', 'p2s_json_person_ids'}
+            'p2s_id_switch_host', 'p2s_id_switch_kernel_ms', 'p2s_json_person_ids', 'p2s_loess_host'}
 
 _lib = None
 

@@ -11,6 +11,10 @@
 // (2 passes x ~6 dependent fp64 operations per sample): a few ms for 100k frames, whatever the number of columns up
 // to the chip's 16k resident lanes; HBM traffic is 5 x 8 B per sample and irrelevant.
 //
+// The other filter types of filtering.py have their kernels further down, each with its own comment: Hampel, Gaussian,
+// median and LOESS (p2s_loess_kernel: local linear regression, filtering.py:532-558) one thread per element, one-euro
+// and Kalman one lane per column, gcv_spline one lane per run.  With LOESS the stage has no filter type left out.
+//
 // p2s_trc_metrics_kernel: Utilities/trc_evaluate.py:114-228 -- per-frame bone lengths and second-difference
 // magnitudes written out for the host's order statistics, sums for means and standard deviations, missing counts.
 #include <hip/hip_runtime.h>
@@ -70,6 +74,15 @@ struct P2sGcvArgs {
     int32_t n_cols, n_runs;
     int32_t auto_mode;           // 1: GCV search of lambda on the normalised run; 0: lambda = fixed_lam on the raw run
     double fixed_lam, smoothing_factor;
+};
+
+// loess_filter_1d: local linear regression over the k nearest samples of a run
+struct P2sLoessArgs {
+    const double *in;            // [n_frames][n_cols]
+    double *out;                 // [n_frames][n_cols]
+    const double *wn;            // [k / 2] the interior window's normalised tricube weights by distance (device)
+    int64_t n_frames, min_run;   // runs of at least min_run samples are filtered
+    int32_t n_cols, k;
 };
 
 struct P2sMetricsArgs {
@@ -216,6 +229,76 @@ __global__ void __launch_bounds__(256) p2s_median_kernel(const P2sColFilterArgs 
         if (less <= want && want < less + eq) med = v;
     }
     a.out[idx] = med;
+}
+
+// loess_filter_1d (filtering.py:532-558) = statsmodels' lowess(run, frame_indices, frac=nb/L, it=0, delta=0) on every run
+// of consecutive non-NaN samples (zeros are data) that is long enough: at sample i the weighted least-squares line
+// through the k run samples nearest to i, evaluated at i.  The k nearest samples of equally spaced abscissae are a
+// contiguous block [l, l + k) of the run, l = i - k / 2 clamped to the run; with h = max(i - l, l + k - 1 - i) the
+// weights are the tricube (1 - (|j - i| / h)^3)^3.  Which of two equally distant neighbours statsmodels keeps only
+// decides whether a sample at distance exactly h is in the window, and its weight is exactly 0: the fit does not depend
+// on it.  A fit with a single non-zero weight (k = 2) returns the sample.  statsmodels is not importable where this was
+// built and has never run here; this follows its published algorithm, and is checked against goldens recorded through
+// the reference's own loess_filter_1d with a stand-in for lowess, and against a 60-digit solve of the definition
+// (tests/golden/loess_units.npz).
+//
+// One thread per element, as for the other window filters.  The sums are taken in abscissae centred on the sample,
+// u = j - i (statsmodels' sums over the frame indices themselves lose about frame index x eps).  Away from the ends of
+// its run the window is symmetric, the slope term vanishes and the fit is a fixed FIR filter: its normalised weights
+// come from the host (wn), pairs added from the far end inwards.
+__host__ __device__ __forceinline__ double loess_tricube(double d, double h) {
+#pragma clang fp contract(off)
+    const double r = d / h;
+    const double t = 1.0 - r * r * r;
+    return t * t * t;
+}
+
+// the filtered value of element idx = frame * n_cols + column
+__host__ __device__ __forceinline__ double loess_at(const P2sLoessArgs &a, int64_t idx) {
+#pragma clang fp contract(off)
+    const int64_t S = a.n_cols, F = a.n_frames, f = idx / S;
+    const double *p = a.in + idx;                              // p[u * S]: the sample u frames on
+    const double x = *p;
+    if (!(x == x)) return x;
+    // valid samples before and after this one, counted as far as the decisions below need them
+    const int64_t cap = a.min_run - 1;
+    int64_t before = 0, after = 0;
+    while (before < cap && f - before > 0 && p[-(before + 1) * S] == p[-(before + 1) * S]) ++before;
+    const int64_t k = a.k, m = k / 2;
+    int64_t lo = before < m ? -before : -m;                    // the window [lo, lo + k) in u, clamped to the run's start
+    const int64_t need = lo + k - 1 > cap - before ? lo + k - 1 : cap - before;
+    while (after < need && f + after < F - 1 && p[(after + 1) * S] == p[(after + 1) * S]) ++after;
+    if (before + after + 1 < a.min_run) return x;              // a run too short to be filtered
+    if (lo + k - 1 > after) lo = after - (k - 1);              // clamped to the run's end
+    const int64_t hi = lo + k - 1;
+    if (lo == -m) {                                            // symmetric: non-zero weights on |u| <= m - 1
+        double acc = 0.0;
+        for (int64_t d = m - 1; d >= 1; --d) acc += (p[-d * S] + p[d * S]) * a.wn[d];
+        return acc + x * a.wn[0];
+    }
+    const int64_t h = -lo > hi ? -lo : hi;
+    const double hd = (double)h;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, t0 = 0.0, t1 = 0.0;
+    int nonzero = 0;
+    for (int64_t u = lo; u <= hi; ++u) {
+        const int64_t d = u < 0 ? -u : u;
+        if (d >= h) continue;                                  // weight exactly 0
+        const double w = loess_tricube((double)d, hd), du = (double)u, v = p[u * S];
+        const double wu = w * du;
+        s0 += w; s1 += wu; s2 += wu * du;
+        t0 += w * v; t1 += wu * v;
+        ++nonzero;
+    }
+    if (nonzero < 2) return x;
+    const double ubar = s1 / s0, ybar = t0 / s0;
+    const double sxx = s2 - s1 * ubar, sxy = t1 - ubar * t0;
+    return ybar - (sxy / sxx) * ubar;                          // the line at u = 0
+}
+
+__global__ void __launch_bounds__(256) p2s_loess_kernel(const P2sLoessArgs a) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= a.n_frames * a.n_cols) return;
+    a.out[idx] = loess_at(a, idx);
 }
 
 // one_euro_filter_1d (filtering.py:87-160): every run of at least two samples that are not NaN goes through the adaptive
@@ -1040,6 +1123,43 @@ int p2s_gcv_spline_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const do
     }
     if (lam_out)
         for (const P2sGcvRun &r : sorted) lam_out[(int64_t)r.start * S + r.col] = r.lam;
+    return P2S_OK;
+}
+
+int p2s_loess_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const double *data, int32_t k, int64_t min_run, double *out) {
+    if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
+    if (n_frames < 0 || n_cols < 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "bad shape: n_frames=%lld n_cols=%d", (long long)n_frames, n_cols);
+    if (k < 2 || k > 8191) return p2s_set_error(P2S_ERR_INVALID_ARG, "LOESS filter: window of %d samples: supported 2..8191", k);
+    if (min_run <= k)
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "LOESS filter: min_run=%lld must exceed the window of %d samples", (long long)min_run, k);
+    if (n_frames == 0 || n_cols == 0) return P2S_OK;
+    if (!data || !out) return p2s_set_error(P2S_ERR_INVALID_ARG, "null pointer");
+    const size_t total = (size_t)n_frames * n_cols, bytes = total * sizeof(double);
+    for (size_t i = 0; i < total; ++i)
+        if (std::isinf(data[i]))
+            return p2s_set_error(P2S_ERR_INVALID_ARG, "LOESS filter: the data hold an infinity (statsmodels' answer for one has not been recorded)");
+
+    // the interior window: tricube weights of the distances 0 .. k / 2 - 1 with h = k / 2, normalised by their sum
+    // over both sides
+    const int m = k / 2;
+    std::vector<double> wn(m);
+    double sum = 0.0;
+    for (int d = m - 1; d >= 1; --d) { wn[d] = loess_tricube((double)d, (double)m); sum += 2.0 * wn[d]; }
+    wn[0] = 1.0;
+    sum += 1.0;
+    for (int d = 0; d < m; ++d) wn[d] /= sum;
+
+    P2sLoessArgs f{};
+    f.n_frames = n_frames; f.n_cols = n_cols; f.k = k; f.min_run = min_run;
+    HIP_TRY(hipSetDevice(ctx->device));
+    Stage st{ctx};
+    P2S_TRY(st.upload(f.in, data, bytes));
+    P2S_TRY(st.alloc(f.out, bytes));
+    P2S_TRY(st.upload(f.wn, wn.data(), (size_t)m * sizeof(double)));
+    hipLaunchKernelGGL(p2s_loess_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, f);
+    HIP_TRY(hipGetLastError());
+    P2S_TRY(st.down(out, f.out, bytes));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return P2S_OK;
 }
 

@@ -34,6 +34,16 @@ def _entry(lib, name):
     return fn
 
 
+def loess_window(nb_values_used):
+    """(k, min_run) of the reference's loess filter for its nb_values_used: statsmodels' lowess takes
+    k = int(frac * n + 1e-10) neighbours with frac = nb / n, and the reference filters the runs with len > nb
+    (filtering.py:552-556)."""
+    nb = float(nb_values_used)
+    if not nb >= 2:
+        raise ValueError(f'loess: nb_values_used = {nb_values_used} gives a window of fewer than 2 samples, whose radius is 0')
+    return int(nb + 1e-10), int(np.floor(nb)) + 1
+
+
 def _cal_arrays(cal, n):
     """K [n][9], dist [n][5] (k1, k2, p1, p2[, k3]), R [n][9], T [n][3] of a calibration dict, contiguous float64."""
     d = np.zeros((n, 5))
@@ -284,6 +294,21 @@ class Engine:
             raise ValueError('Regularization parameter should be non-negative')
         _lib.check(rc)
         return out, lam_out
+
+    def loess(self, data, nb_values_used):
+        """loess_filter_1d (filtering.py:532-558) on every column of data [n_frames][n_cols]: every run of more than
+        nb_values_used consecutive non-NaN samples (zeros are data) is replaced by its local linear regression over the
+        k = int(nb_values_used + 1e-10) nearest samples with tricube weights -- statsmodels' lowess with
+        frac = nb_values_used / len(run), it = 0 -- and every other sample is copied.  nb_values_used < 2 raises
+        ValueError: a window of one sample has radius 0."""
+        fn = _entry(self._lib, 'p2s_loess_host')
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        if data.ndim != 2:
+            raise P2sError(f'data has shape {data.shape}; expected [n_frames][n_cols]')
+        k, min_run = loess_window(nb_values_used)
+        out = np.empty_like(data)
+        _lib.check(fn(self._h, data.shape[0], data.shape[1], _optr(data), k, min_run, _optr(out)))
+        return out
 
     def trc_metrics(self, xyz, bones):
         """trc_evaluate's per-frame quantities for xyz [F][K][3] and bones [n][2] (parent, child marker indices):

@@ -21,9 +21,16 @@ What runs where:
   P, R, Q, the ``smooth`` test, run splitting) was executed with a stand-in for filterpy's recursion, the stand-in being
   checked against an exact multiprecision solve of the same model (tests/golden/make_golden_kalman.py)
 
+* ``loess`` (:532-558) ..................................................... p2s_loess_kernel: local linear regression
+  with tricube weights over the nb_values_used nearest samples of every run of more than nb_values_used non-NaN
+  samples.  The reference takes it from statsmodels' lowess, which is not importable where this was built and has never
+  run here: parity-unpinned against statsmodels.  The kernel follows the published algorithm and is pinned by goldens
+  for which the reference's own loess_filter_1d was executed with a stand-in for lowess, the stand-in being checked
+  against an exact multiprecision solve of the definition (tests/golden/make_golden_loess.py)
+
 Coefficients and kernel weights come from the very SciPy calls the reference makes, so the kernels reproduce its numbers
-to rounding.  ``loess`` needs statsmodels, which is not importable where this was built: it is refused with
-NotImplementedError.  The figures of the reference (``display_figures``, ``save_filt_plots``) are a GUI matter and not produced.
+to rounding.  Every filter type of the reference's filter_mapping runs.  The figures of the reference
+(``display_figures``, ``save_filt_plots``) are a GUI matter and not produced.
 """
 import glob
 import logging
@@ -34,7 +41,6 @@ import numpy as np
 from . import trc as trc_mod
 
 FILTER_HAMPEL, FILTER_GAUSSIAN, FILTER_MEDIAN, FILTER_ONE_EURO, FILTER_KALMAN = 1, 2, 3, 4, 5    # include/p2s.h
-REFUSED_TYPES = {'loess': 'statsmodels'}
 
 
 def _make_engine():
@@ -123,6 +129,18 @@ def gcv_spline_filter(data, cutoff, smoothing_factor, frame_rate, engine=None):
     return out
 
 
+def loess_filter(data, nb_values_used, engine=None):
+    """loess_filter_1d (filtering.py:532-558) on every column: every run of more than nb_values_used consecutive non-NaN
+    samples (zeros are data here) is replaced by statsmodels' lowess(run, frames, frac=nb_values_used / len(run), it=0),
+    the local linear regression over the int(nb_values_used + 1e-10) nearest samples with tricube weights.  statsmodels
+    has never run where this was built: the kernel follows its published algorithm.  nb_values_used < 2
+    raises ValueError; an engine without loess (or whose library lacks the entry point) raises NotImplementedError."""
+    engine = engine or _make_engine()
+    if not hasattr(engine, 'loess'):
+        raise NotImplementedError("filter type 'loess' needs an engine with loess, which this one lacks")
+    return engine.loess(data, nb_values_used)
+
+
 def _apply(filter_type, fcfg, data, frame_rate, engine):
     """filter1d (filtering.py:632-662) for a whole matrix."""
     if filter_type == 'butterworth':
@@ -144,8 +162,9 @@ def _apply(filter_type, fcfg, data, frame_rate, engine):
     if filter_type == 'gcv_spline':
         p = _sub(fcfg, 'gcv_spline')
         return gcv_spline_filter(data, p.get('cut_off_frequency', 'auto'), p.get('smoothing_factor', 1.0), frame_rate, engine)
-    if filter_type in REFUSED_TYPES:
-        raise NotImplementedError(f"filter type '{filter_type}' needs {REFUSED_TYPES[filter_type]}, which is not part of this build")
+    if filter_type == 'loess':
+        p = fcfg.get('loess', fcfg.get('LOESS'))               # the reference reads either key (:545)
+        return loess_filter(data, (p if isinstance(p, dict) else {}).get('nb_values_used'), engine)
     raise KeyError(filter_type)                                # the reference's filter_mapping[filter_type]
 
 
@@ -179,6 +198,7 @@ _TYPE_LINES = {
     'butterworth_on_speed': lambda f: (f"--> Filter type: Butterworth on speed low-pass. Order {int(_sub(f, 'butterworth_on_speed').get('order'))}, "
                                        f"Cut-off frequency {int(_sub(f, 'butterworth_on_speed').get('cut_off_frequency'))} Hz."),
     'gaussian': lambda f: f"--> Filter type: Gaussian. Standard deviation kernel: {int(_sub(f, 'gaussian').get('sigma_kernel'))}",
+    'loess': lambda f: f"--> Filter type: LOESS. Number of values used: {f.get('loess', f.get('LOESS')).get('nb_values_used')}",
     'median': lambda f: f"--> Filter type: Median. Kernel size: {_sub(f, 'median').get('kernel_size')}",
     'gcv_spline': lambda f: (f"--> Filter type: Generalized Cross-Validation Spline. Optimal parameters automatically estimated with smoothing factor "
                              f"{float(_sub(f, 'gcv_spline').get('smoothing_factor', 1.0))}."
@@ -190,7 +210,7 @@ _TYPE_LINES = {
 
 
 def recap_filter3d(config_dict, trc_path):
-    """The stage's report (filtering.py:665-725) for the filter types this build runs."""
+    """The stage's report (filtering.py:665-725) for every filter type."""
     fcfg = config_dict.get('filtering')
     say = logging.info
     say('--> Outliers rejected with a Hampel filter.' if fcfg.get('reject_outliers', False)
@@ -234,9 +254,6 @@ def filter_all(config_dict, engine=None):
     reject_outliers = fcfg.get('reject_outliers', False)
     filter_type = fcfg.get('type')
     frame_range = config_dict.get('project').get('frame_range')
-    if do_filter and filter_type in REFUSED_TYPES:
-        raise NotImplementedError(f"filter type '{filter_type}' needs {REFUSED_TYPES[filter_type]}, which is not part of this build; "
-                                  f"supported: {sorted(_TYPE_LINES)}")
     frame_rate = _frame_rate(config_dict, project_dir)
 
     written = []
