@@ -40,7 +40,7 @@ extern "C" {
 #define P2S_ERR_HIP (-2)
 #define P2S_ERR_NO_DEVICE (-3)
 #define P2S_ERR_NO_CALIB (-4)
-#define P2S_ERR_OOM (-5)
+#define P2S_ERR_OOM (-5)                /* device or host memory; what the call wrote to its outputs is unspecified */
 
 #define P2S_F32 0
 #define P2S_F64 1

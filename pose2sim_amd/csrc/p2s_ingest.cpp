@@ -17,7 +17,6 @@
 #include <cstring>
 #include <limits>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include <errno.h>
@@ -27,6 +26,7 @@
 
 #include "p2s.h"
 #include "p2s_error.h"
+#include "p2s_host.h"
 
 namespace {
 
@@ -487,79 +487,6 @@ struct Parser {
     }
 };
 
-// Strict UTF-8 (what open(path, 'r') decodes with): no overlongs, no surrogates, <= U+10FFFF.
-bool valid_utf8(const unsigned char *s, size_t n) {
-    size_t i = 0;
-    while (i < n) {
-        const unsigned char c = s[i];
-        if (c < 0x80) {
-            ++i;
-            continue;
-        }
-        int len;
-        uint32_t cp;
-        if ((c & 0xE0) == 0xC0) { len = 2; cp = c & 0x1F; }
-        else if ((c & 0xF0) == 0xE0) { len = 3; cp = c & 0x0F; }
-        else if ((c & 0xF8) == 0xF0) { len = 4; cp = c & 0x07; }
-        else return false;
-        if (i + len > n) return false;
-        for (int k = 1; k < len; ++k) {
-            if ((s[i + k] & 0xC0) != 0x80) return false;
-            cp = (cp << 6) | (s[i + k] & 0x3F);
-        }
-        if ((len == 2 && cp < 0x80) || (len == 3 && cp < 0x800) || (len == 4 && cp < 0x10000)) return false;
-        if (cp > 0x10FFFF || (cp >= 0xD800 && cp <= 0xDFFF)) return false;
-        i += len;
-    }
-    return true;
-}
-
-bool read_file(const char *path, std::vector<char> &buf, size_t &n) {
-    const int fd = open(path, O_RDONLY | O_CLOEXEC);
-    if (fd < 0) return false;
-    n = 0;
-    if (buf.size() < 16384) buf.resize(16384);
-    while (true) {
-        if (n == buf.size()) buf.resize(buf.size() * 2);
-        const ssize_t r = read(fd, buf.data() + n, buf.size() - n);
-        if (r < 0) {
-            close(fd);
-            return false;
-        }
-        if (r == 0) break;
-        n += (size_t)r;
-    }
-    close(fd);
-    return true;
-}
-
-int pick_threads(int32_t n_threads, int64_t work) {
-    int n = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    if (n < 1) n = 1;
-    if (n > 64) n = 64;
-    if ((int64_t)n > work) n = (int)(work > 0 ? work : 1);
-    return n;
-}
-
-template <typename Fn>
-void parallel_for(int64_t n, int n_threads, int64_t grain, Fn fn) {
-    if (n_threads <= 1) {
-        fn(0, (int64_t)0, n);
-        return;
-    }
-    std::atomic<int64_t> next{0};
-    std::vector<std::thread> pool;
-    for (int t = 0; t < n_threads; ++t)
-        pool.emplace_back([&, t] {
-            while (true) {
-                const int64_t b = next.fetch_add(grain);
-                if (b >= n) break;
-                fn(t, b, b + grain < n ? b + grain : n);
-            }
-        });
-    for (auto &th : pool) th.join();
-}
-
 }  // namespace
 
 struct p2s_json_batch {
@@ -584,10 +511,10 @@ int p2s_json_parse(const char *paths, const int64_t *path_offsets, int64_t n_fil
     if (!b) return p2s_set_error(P2S_ERR_OOM, "out of host memory");
     try {
         b->n_files = n_files;
-        b->n_threads = pick_threads(n_threads, n_files / 64 + 1);
+        b->n_threads = host_threads(n_threads, 64, n_files / 64 + 1);
         b->files.resize((size_t)n_files);
         b->arenas.resize((size_t)b->n_threads);
-        parallel_for(n_files, b->n_threads, 64, [&](int t, int64_t lo, int64_t hi) {
+        const bool done = parallel_for(n_files, b->n_threads, 64, [&](int t, int64_t lo, int64_t hi) {
             Arena &arena = b->arenas[(size_t)t];
             std::string path;
             for (int64_t i = lo; i < hi; ++i) {
@@ -610,6 +537,7 @@ int p2s_json_parse(const char *paths, const int64_t *path_offsets, int64_t n_fil
                 fr.flags = ps.file_flags;
             }
         });
+        if (!done) throw std::bad_alloc();
         b->person_base.resize((size_t)n_files + 1);
         b->person_base[0] = 0;
         for (int64_t i = 0; i < n_files; ++i)
@@ -662,12 +590,13 @@ inline void store_value(T *dst, double v, int64_t &inexact) {
     *dst = t;
 }
 
+// The gathers return how many values float32 cannot hold exactly, -1 when a worker ran out of memory.
 template <typename T>
 int64_t gather_keypoints(const p2s_json_batch *b, const int32_t *ids, int32_t n_ids, int32_t max_persons,
                          const int64_t *file_offsets, int64_t person_stride, T *out) {
     std::atomic<int64_t> inexact_total{0};
     const T nan = std::numeric_limits<T>::quiet_NaN();
-    parallel_for(b->n_files, pick_threads(b->n_threads, b->n_files / 256 + 1), 256, [&](int, int64_t lo, int64_t hi) {
+    const bool done = parallel_for(b->n_files, host_threads(b->n_threads, 64, b->n_files / 256 + 1), 256, [&](int, int64_t lo, int64_t hi) {
         int64_t inexact = 0;
         for (int64_t i = lo; i < hi; ++i) {
             const FileRec &fr = b->files[(size_t)i];
@@ -694,7 +623,7 @@ int64_t gather_keypoints(const p2s_json_batch *b, const int32_t *ids, int32_t n_
         }
         inexact_total.fetch_add(inexact);
     });
-    return inexact_total.load();
+    return done ? inexact_total.load() : -1;
 }
 
 template <typename T>
@@ -702,7 +631,7 @@ int64_t gather_people(const p2s_json_batch *b, const int64_t *file_of, const int
                       int32_t n_values, T *out) {
     std::atomic<int64_t> inexact_total{0};
     const T nan = std::numeric_limits<T>::quiet_NaN();
-    parallel_for(n_rows, pick_threads(b->n_threads, n_rows / 1024 + 1), 1024, [&](int, int64_t lo, int64_t hi) {
+    const bool done = parallel_for(n_rows, host_threads(b->n_threads, 64, n_rows / 1024 + 1), 1024, [&](int, int64_t lo, int64_t hi) {
         int64_t inexact = 0;
         for (int64_t r = lo; r < hi; ++r) {
             T *dst = out + r * (int64_t)n_values;
@@ -716,7 +645,7 @@ int64_t gather_people(const p2s_json_batch *b, const int64_t *file_of, const int
         }
         inexact_total.fetch_add(inexact);
     });
-    return inexact_total.load();
+    return done ? inexact_total.load() : -1;
 }
 
 
@@ -762,13 +691,13 @@ bool largest_person(const p2s_json_batch *b, int64_t i, const int32_t *ids, int3
 }
 
 bool copy_one(const std::string &src, const std::string &dst, std::vector<char> &buf, int &err) {
+    if (buf.size() < (1 << 16)) buf.resize(1 << 16);             // before a descriptor is open: resize may throw
     const int in = open(src.c_str(), O_RDONLY | O_CLOEXEC);
     if (in < 0) { err = errno; return false; }
     struct stat st;
     if (fstat(in, &st) != 0) { err = errno; close(in); return false; }
     const int out = open(dst.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
     if (out < 0) { err = errno; close(in); return false; }
-    if (buf.size() < (1 << 16)) buf.resize(1 << 16);
     bool ok = true;
     while (ok) {
         const ssize_t r = read(in, buf.data(), buf.size());
@@ -799,6 +728,7 @@ int p2s_json_gather_keypoints(const p2s_json_batch *b, const int32_t *keypoint_i
     const int64_t bad = dtype == P2S_F32
         ? gather_keypoints<float>(b, keypoint_ids, n_ids, max_persons, file_offsets, person_stride, (float *)out)
         : gather_keypoints<double>(b, keypoint_ids, n_ids, max_persons, file_offsets, person_stride, (double *)out);
+    if (bad < 0) return p2s_set_error(P2S_ERR_OOM, "out of host memory");
     if (n_inexact) *n_inexact = bad;
     return P2S_OK;
 }
@@ -818,6 +748,7 @@ int p2s_json_gather_people(const p2s_json_batch *b, const int64_t *file_index, c
     }
     const int64_t bad = dtype == P2S_F32 ? gather_people<float>(b, file_index, person_index, n_rows, n_values, (float *)out)
                                          : gather_people<double>(b, file_index, person_index, n_rows, n_values, (double *)out);
+    if (bad < 0) return p2s_set_error(P2S_ERR_OOM, "out of host memory");
     if (n_inexact) *n_inexact = bad;
     return P2S_OK;
 }
@@ -828,14 +759,14 @@ int p2s_json_gather_largest_person(const p2s_json_batch *b, const int32_t *keypo
         return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
     if (n_ids < 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "negative size");
     const double nan = std::numeric_limits<double>::quiet_NaN();
-    parallel_for(b->n_files, pick_threads(b->n_threads, b->n_files / 256 + 1), 256, [&](int, int64_t lo, int64_t hi) {
+    const bool done = parallel_for(b->n_files, host_threads(b->n_threads, 64, b->n_files / 256 + 1), 256, [&](int, int64_t lo, int64_t hi) {
         for (int64_t i = lo; i < hi; ++i) {
             double *dst = out + i * (int64_t)n_ids * 3;
             if (!largest_person(b, i, keypoint_ids, n_ids, likelihood_threshold, dst))
                 for (int64_t k = 0; k < (int64_t)n_ids * 3; ++k) dst[k] = nan;   // the except branch: all NaN
         }
     });
-    return P2S_OK;
+    return done ? P2S_OK : p2s_set_error(P2S_ERR_OOM, "out of host memory");
 }
 
 int p2s_json_person_ids(const p2s_json_batch *b, int64_t *text_off, char *text, int64_t text_capacity, int32_t *file_kind) {
@@ -855,7 +786,7 @@ int p2s_json_person_ids(const p2s_json_batch *b, int64_t *text_off, char *text, 
         for (int32_t n = 0; n < fr.count; ++n) {
             const Person &ps = arena.persons[(size_t)(fr.first_person + n)];
             text_off[b->person_base[(size_t)i] + n] = at;
-            if (text && at + ps.id_len <= text_capacity) memcpy(text + at, arena.texts.data() + ps.id_off, (size_t)ps.id_len);
+            if (text && ps.id_len && at + ps.id_len <= text_capacity) memcpy(text + at, arena.texts.data() + ps.id_off, (size_t)ps.id_len);
             at += ps.id_len;
         }
     }
@@ -970,7 +901,7 @@ int p2s_copy_files(const char *src_paths, const int64_t *src_offsets, const char
         return p2s_set_error(P2S_ERR_INVALID_ARG, "bad path table");
     std::atomic<int64_t> first_bad{n_files};
     std::vector<int> errs((size_t)n_files, 0);
-    parallel_for(n_files, pick_threads(n_threads, n_files / 64 + 1), 64, [&](int, int64_t lo, int64_t hi) {
+    const bool all_run = parallel_for(n_files, host_threads(n_threads, 64, n_files / 64 + 1), 64, [&](int, int64_t lo, int64_t hi) {
         std::vector<char> buf;
         std::string src, dst;
         for (int64_t i = lo; i < hi; ++i) {
@@ -986,6 +917,7 @@ int p2s_copy_files(const char *src_paths, const int64_t *src_offsets, const char
             }
         }
     });
+    if (!all_run) return p2s_set_error(P2S_ERR_OOM, "out of host memory while copying");
     const int64_t bad = first_bad.load();
     if (bad < n_files) {
         const std::string src(src_paths + src_offsets[bad], (size_t)(src_offsets[bad + 1] - src_offsets[bad]));

@@ -8,13 +8,20 @@
 // first-come filter -- stays in NumPy on purpose: np.argsort's order among equal counts is not specified (the
 // AVX-512 sorting networks of NumPy 2.x are not stable even for 7 elements) and it decides which person comes
 // first in the rewritten JSON files, so the caller runs the very same NumPy calls as the reference.
-#include <atomic>
 #include <cstdint>
-#include <thread>
 #include <vector>
 
 #include "p2s.h"
 #include "p2s_error.h"
+#include "p2s_host.h"
+
+// body(f) for every frame on at most 32 host threads, 256 frames to a chunk; false when a body ran out of memory.
+template <typename F>
+static bool for_frames(int64_t n_frames, int32_t n_threads, F body) {
+    return parallel_for(n_frames, host_threads(n_threads, 32, n_frames / 256 + 1), 256, [&](int, int64_t lo, int64_t hi) {
+        for (int64_t f = lo; f < hi; ++f) body(f);
+    });
+}
 
 extern "C" int p2s_assoc_argmax_rows(int64_t n_frames, int32_t n_cams, int32_t n_max, const double *affinity,
                                      const int32_t *n_persons, int32_t n_threads, int32_t *rows) {
@@ -28,47 +35,29 @@ extern "C" int p2s_assoc_argmax_rows(int64_t n_frames, int32_t n_cams, int32_t n
         }
         if (tot > n_max) return p2s_set_error(P2S_ERR_INVALID_ARG, "frame %lld holds more detections than n_max", (long long)f);
     }
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    if (nt < 1) nt = 1;
-    if (nt > 32) nt = 32;
-    if ((int64_t)nt > n_frames / 256 + 1) nt = (int)(n_frames / 256 + 1);
-    std::atomic<int64_t> next{0};
-    auto work = [&] {
-        while (true) {
-            const int64_t lo = next.fetch_add(256);
-            if (lo >= n_frames) break;
-            const int64_t hi = lo + 256 < n_frames ? lo + 256 : n_frames;
-            for (int64_t f = lo; f < hi; ++f) {
-                const double *aff = affinity + f * (int64_t)n_max * n_max;
-                const int32_t *np_ = n_persons + f * n_cams;
-                int32_t *out = rows + f * (int64_t)n_max * n_cams;
-                int cum[P2S_MAX_CAMS + 1];
-                cum[0] = 0;
-                for (int c = 0; c < n_cams; ++c) cum[c + 1] = cum[c] + np_[c];
-                const int N = cum[n_cams];
-                for (int r = 0; r < N; ++r)
-                    for (int c = 0; c < n_cams; ++c) {
-                        int best = -1;
-                        double bv = 0.0;
-                        bool has_nan = false;
-                        for (int j = cum[c]; j < cum[c + 1]; ++j) {
-                            const double v = aff[(int64_t)r * n_max + j];
-                            if (v != v) { has_nan = true; if (best < 0 || !(bv != bv)) { best = j - cum[c]; bv = v; } break; }   // np.argmax: first NaN wins
-                            if (best < 0 || v > bv) { best = j - cum[c]; bv = v; }                                          // first maximum
-                        }
-                        // `max(block) > 0` is False for a NaN maximum as well
-                        out[(int64_t)r * n_cams + c] = (best >= 0 && !has_nan && bv > 0.0) ? best : -1;
-                    }
+    const bool done = for_frames(n_frames, n_threads, [&](int64_t f) {
+        const double *aff = affinity + f * (int64_t)n_max * n_max;
+        const int32_t *np_ = n_persons + f * n_cams;
+        int32_t *out = rows + f * (int64_t)n_max * n_cams;
+        int cum[P2S_MAX_CAMS + 1];
+        cum[0] = 0;
+        for (int c = 0; c < n_cams; ++c) cum[c + 1] = cum[c] + np_[c];
+        const int N = cum[n_cams];
+        for (int r = 0; r < N; ++r)
+            for (int c = 0; c < n_cams; ++c) {
+                int best = -1;
+                double bv = 0.0;
+                bool has_nan = false;
+                for (int j = cum[c]; j < cum[c + 1]; ++j) {
+                    const double v = aff[(int64_t)r * n_max + j];
+                    if (v != v) { has_nan = true; if (best < 0 || !(bv != bv)) { best = j - cum[c]; bv = v; } break; }   // np.argmax: first NaN wins
+                    if (best < 0 || v > bv) { best = j - cum[c]; bv = v; }                                          // first maximum
+                }
+                // `max(block) > 0` is False for a NaN maximum as well
+                out[(int64_t)r * n_cams + c] = (best >= 0 && !has_nan && bv > 0.0) ? best : -1;
             }
-        }
-    };
-    if (nt <= 1) work();
-    else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < nt; ++t) pool.emplace_back(work);
-        for (auto &th : pool) th.join();
-    }
-    return P2S_OK;
+    });
+    return done ? P2S_OK : p2s_set_error(P2S_ERR_OOM, "out of host memory");
 }
 
 
@@ -77,34 +66,13 @@ extern "C" int p2s_assoc_argmax_rows(int64_t n_frames, int32_t n_cams, int32_t n
 // multiplicities) and so is everything after np.argsort(counts)[::-1]: the first-come filter (a proposal that reuses, for
 // some camera, a person of ANY proposal ranked before it is dropped) and the minimum number of cameras.  Both halves are
 // done here for every frame at once; the caller makes the argsort call itself, on the very array the reference would pass.
-template <typename F>
-static void for_frames(int64_t n_frames, int32_t n_threads, F &&body) {
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    if (nt < 1) nt = 1;
-    if (nt > 32) nt = 32;
-    if ((int64_t)nt > n_frames / 256 + 1) nt = (int)(n_frames / 256 + 1);
-    std::atomic<int64_t> next{0};
-    auto work = [&] {
-        while (true) {
-            const int64_t lo = next.fetch_add(256);
-            if (lo >= n_frames) break;
-            const int64_t hi = lo + 256 < n_frames ? lo + 256 : n_frames;
-            for (int64_t f = lo; f < hi; ++f) body(f);
-        }
-    };
-    if (nt <= 1) { work(); return; }
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nt; ++t) pool.emplace_back(work);
-    for (auto &th : pool) th.join();
-}
-
 extern "C" int p2s_assoc_unique_rows(int64_t n_frames, int32_t n_cams, int32_t n_max, const int32_t *rows, const int32_t *n_rows,
                                      int32_t n_threads, int32_t *uniq, int64_t *counts, int32_t *n_uniq) {
     if (n_frames < 0 || n_cams < 1 || n_cams > P2S_MAX_CAMS || n_max < 0 || (n_frames > 0 && (!rows || !n_rows || !uniq || !counts || !n_uniq)))
         return p2s_set_error(P2S_ERR_INVALID_ARG, "bad arguments");
     for (int64_t f = 0; f < n_frames; ++f)
         if (n_rows[f] < 0 || n_rows[f] > n_max) return p2s_set_error(P2S_ERR_INVALID_ARG, "frame %lld: %d rows of at most %d", (long long)f, n_rows[f], n_max);
-    for_frames(n_frames, n_threads, [&](int64_t f) {
+    const bool done = for_frames(n_frames, n_threads, [&](int64_t f) {
         const int32_t *in = rows + f * (int64_t)n_max * n_cams;
         int32_t *out = uniq + f * (int64_t)n_max * n_cams;
         int64_t *cnt = counts + f * (int64_t)n_max;
@@ -135,7 +103,7 @@ extern "C" int p2s_assoc_unique_rows(int64_t n_frames, int32_t n_cams, int32_t n
         }
         n_uniq[f] = u;
     });
-    return P2S_OK;
+    return done ? P2S_OK : p2s_set_error(P2S_ERR_OOM, "out of host memory");
 }
 
 extern "C" int p2s_assoc_filter_rows(int64_t n_frames, int32_t n_cams, int32_t n_max, const int32_t *uniq, const int32_t *n_uniq,
@@ -148,7 +116,7 @@ extern "C" int p2s_assoc_filter_rows(int64_t n_frames, int32_t n_cams, int32_t n
             if (rank[f * (int64_t)n_max + i] < 0 || rank[f * (int64_t)n_max + i] >= n_uniq[f])
                 return p2s_set_error(P2S_ERR_INVALID_ARG, "frame %lld: rank out of range", (long long)f);
     }
-    for_frames(n_frames, n_threads, [&](int64_t f) {
+    const bool done = for_frames(n_frames, n_threads, [&](int64_t f) {
         const int32_t *in = uniq + f * (int64_t)n_max * n_cams;
         const int32_t *rk = rank + f * (int64_t)n_max;
         int32_t *out = props + f * (int64_t)n_max * n_cams;
@@ -169,5 +137,5 @@ extern "C" int p2s_assoc_filter_rows(int64_t n_frames, int32_t n_cams, int32_t n
         }
         n_props[f] = kept;
     });
-    return P2S_OK;
+    return done ? P2S_OK : p2s_set_error(P2S_ERR_OOM, "out of host memory");
 }

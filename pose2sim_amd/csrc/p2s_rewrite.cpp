@@ -7,7 +7,6 @@
 // first-occurrence order with the last value of a repeated key, strings re-escaped with ensure_ascii, ints as
 // str(int), floats as repr(float) / NaN / Infinity.  This file reproduces that text directly from the source bytes
 // (one pass, no DOM), so that writing 400 k files stops costing a minute of json.load / json.dumps.
-#include <atomic>
 #include <charconv>
 #include <cmath>
 #include <cstdint>
@@ -15,7 +14,6 @@
 #include <cstring>
 #include <limits>
 #include <string>
-#include <thread>
 #include <utility>
 #include <vector>
 
@@ -24,6 +22,7 @@
 
 #include "p2s.h"
 #include "p2s_error.h"
+#include "p2s_host.h"
 extern "C" int p2s_format_float_repr(double value, char *out, int32_t capacity);   // p2s_trc.cpp
 
 namespace {
@@ -278,45 +277,6 @@ struct Transcoder {
     }
 };
 
-bool valid_utf8(const unsigned char *s, size_t n) {
-    size_t i = 0;
-    while (i < n) {
-        const unsigned char c = s[i];
-        if (c < 0x80) { ++i; continue; }
-        int len;
-        uint32_t cp;
-        if ((c & 0xE0) == 0xC0) { len = 2; cp = c & 0x1F; }
-        else if ((c & 0xF0) == 0xE0) { len = 3; cp = c & 0x0F; }
-        else if ((c & 0xF8) == 0xF0) { len = 4; cp = c & 0x07; }
-        else return false;
-        if (i + len > n) return false;
-        for (int k = 1; k < len; ++k) {
-            if ((s[i + k] & 0xC0) != 0x80) return false;
-            cp = (cp << 6) | (s[i + k] & 0x3F);
-        }
-        if ((len == 2 && cp < 0x80) || (len == 3 && cp < 0x800) || (len == 4 && cp < 0x10000)) return false;
-        if (cp > 0x10FFFF || (cp >= 0xD800 && cp <= 0xDFFF)) return false;
-        i += len;
-    }
-    return true;
-}
-
-bool read_all(const char *path, std::vector<char> &buf, size_t &n) {
-    const int fd = open(path, O_RDONLY | O_CLOEXEC);
-    if (fd < 0) return false;
-    n = 0;
-    if (buf.size() < 16384) buf.resize(16384);
-    while (true) {
-        if (n == buf.size()) buf.resize(buf.size() * 2);
-        const ssize_t r = read(fd, buf.data() + n, buf.size() - n);
-        if (r < 0) { close(fd); return false; }
-        if (r == 0) break;
-        n += (size_t)r;
-    }
-    close(fd);
-    return true;
-}
-
 // The text json.dumps(js_new) of rewrite_json_files for one source document, or false when the reference
 // would have raised (unreadable, not JSON, no usable 'people' list, index out of range).
 bool rewrite_document(const char *src, size_t n, const int32_t *sel, int32_t n_sel, std::string &out) {
@@ -419,58 +379,35 @@ int p2s_json_rewrite_people(const char *src_paths, const int64_t *src_offsets, c
         if (src_offsets[i + 1] < src_offsets[i] || dst_offsets[i + 1] < dst_offsets[i] || sel_offsets[i + 1] < sel_offsets[i])
             return p2s_set_error(P2S_ERR_INVALID_ARG, "offsets must not decrease");
     if (n_files > 0 && sel_offsets[n_files] > sel_offsets[0] && !sel) return p2s_set_error(P2S_ERR_INVALID_ARG, "null selection");
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    if (nt < 1) nt = 1;
-    if (nt > 64) nt = 64;
-    if ((int64_t)nt > n_files / 32 + 1) nt = (int)(n_files / 32 + 1);
-    std::atomic<int64_t> next{0};
-    std::atomic<int> oom{0};
-    auto work = [&] {
+    const bool done = parallel_for(n_files, host_threads(n_threads, 64, n_files / 32 + 1), 32, [&](int, int64_t lo, int64_t hi) {
         std::vector<char> buf;
         std::string out, src, dst;
-        try {
-            while (true) {
-                const int64_t lo = next.fetch_add(32);
-                if (lo >= n_files) break;
-                const int64_t hi = lo + 32 < n_files ? lo + 32 : n_files;
-                for (int64_t i = lo; i < hi; ++i) {
-                    src.assign(src_paths + src_offsets[i], (size_t)(src_offsets[i + 1] - src_offsets[i]));
-                    dst.assign(dst_paths + dst_offsets[i], (size_t)(dst_offsets[i + 1] - dst_offsets[i]));
-                    bool ok = false;
-                    // open(dst, 'w') comes first in the reference: a destination that cannot be created is an
-                    // error of its own there; here the file simply is not written
-                    const int fd = open(dst.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
-                    if (fd >= 0) {
-                        size_t n = 0;
-                        if (!src.empty() && read_all(src.c_str(), buf, n) &&
-                            rewrite_document(buf.data(), n, sel + sel_offsets[i], (int32_t)(sel_offsets[i + 1] - sel_offsets[i]), out)) {
-                            size_t done = 0;
-                            ok = true;
-                            while (done < out.size()) {
-                                const ssize_t w = write(fd, out.data() + done, out.size() - done);
-                                if (w <= 0) { ok = false; break; }
-                                done += (size_t)w;
-                            }
-                        }
-                        close(fd);
-                        if (!ok) unlink(dst.c_str());      // except: os.remove(json_tracked_files_f[cam])
+        for (int64_t i = lo; i < hi; ++i) {
+            src.assign(src_paths + src_offsets[i], (size_t)(src_offsets[i + 1] - src_offsets[i]));
+            dst.assign(dst_paths + dst_offsets[i], (size_t)(dst_offsets[i + 1] - dst_offsets[i]));
+            bool ok = false;
+            // open(dst, 'w') comes first in the reference: a destination that cannot be created is an
+            // error of its own there; here the file simply is not written
+            const int fd = open(dst.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+            if (fd >= 0) {
+                size_t n = 0;
+                if (!src.empty() && read_file(src.c_str(), buf, n) &&
+                    rewrite_document(buf.data(), n, sel + sel_offsets[i], (int32_t)(sel_offsets[i + 1] - sel_offsets[i]), out)) {
+                    size_t at = 0;
+                    ok = true;
+                    while (at < out.size()) {
+                        const ssize_t w = write(fd, out.data() + at, out.size() - at);
+                        if (w <= 0) { ok = false; break; }
+                        at += (size_t)w;
                     }
-                    if (written) written[i] = ok ? 1 : 0;
                 }
+                close(fd);
+                if (!ok) unlink(dst.c_str());      // except: os.remove(json_tracked_files_f[cam])
             }
-        } catch (const std::bad_alloc &) {
-            oom.store(1);
+            if (written) written[i] = ok ? 1 : 0;
         }
-    };
-    if (nt <= 1) {
-        work();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < nt; ++t) pool.emplace_back(work);
-        for (auto &th : pool) th.join();
-    }
-    if (oom.load()) return p2s_set_error(P2S_ERR_OOM, "out of host memory while rewriting");
-    return P2S_OK;
+    });
+    return done ? P2S_OK : p2s_set_error(P2S_ERR_OOM, "out of host memory while rewriting");
 }
 
 }  // extern "C"

@@ -10,12 +10,12 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 #include <atomic>
 
 #include "p2s.h"
 #include "p2s_error.h"
+#include "p2s_host.h"
 
 namespace {
 
@@ -110,9 +110,7 @@ int p2s_trc_append_rows(const char *path, int64_t n_rows, int32_t n_cols, const 
         return p2s_set_error(P2S_ERR_INVALID_ARG, "bad arguments");
     FILE *fh = fopen(path, "ab");
     if (!fh) return p2s_set_error(P2S_ERR_INVALID_ARG, "cannot open %s for appending", path);
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    if (nt < 1) nt = 1;
-    if (nt > 32) nt = 32;
+    const int nt = host_threads(n_threads, 32, 32);           // not clamped to the rows: a group is nt blocks
     const int64_t block = 4096;                               // rows formatted per task
     const size_t row_cap = 48 + (size_t)n_cols * 26;
     int rc = P2S_OK;
@@ -121,32 +119,30 @@ int p2s_trc_append_rows(const char *path, int64_t n_rows, int32_t n_cols, const 
         std::vector<std::vector<char>> bufs((size_t)nt);
         std::vector<size_t> used((size_t)nt);
         for (int64_t g0 = 0; g0 < n_rows && rc == P2S_OK; g0 += block * nt) {
-            std::vector<std::thread> pool;
-            for (int t = 0; t < nt; ++t) {
-                const int64_t lo = g0 + (int64_t)t * block;
-                if (lo >= n_rows) { used[(size_t)t] = 0; continue; }
+            const int64_t left = (n_rows - g0 + block - 1) / block;
+            const int n_blocks = (int)(left < nt ? left : nt);
+            const bool done = parallel_for(n_blocks, n_blocks, 1, [&](int, int64_t slot, int64_t) {
+                const int64_t lo = g0 + slot * block;
                 const int64_t hi = lo + block < n_rows ? lo + block : n_rows;
-                pool.emplace_back([&, t, lo, hi] {
-                    std::vector<char> &b = bufs[(size_t)t];
-                    b.resize((size_t)(hi - lo) * row_cap);
-                    char *o = b.data();
-                    for (int64_t r = lo; r < hi; ++r) {
-                        o = put_int(o, frames[r]);
+                std::vector<char> &b = bufs[(size_t)slot];
+                b.resize((size_t)(hi - lo) * row_cap);
+                char *o = b.data();
+                for (int64_t r = lo; r < hi; ++r) {
+                    o = put_int(o, frames[r]);
+                    *o++ = '\t';
+                    o = py_repr(o, time[r]);
+                    const double *row = data + r * (int64_t)n_cols;
+                    for (int32_t c = 0; c < n_cols; ++c) {
                         *o++ = '\t';
-                        o = py_repr(o, time[r]);
-                        const double *row = data + r * (int64_t)n_cols;
-                        for (int32_t c = 0; c < n_cols; ++c) {
-                            *o++ = '\t';
-                            o = py_repr(o, row[c]);
-                        }
-                        *o++ = '\n';
+                        o = py_repr(o, row[c]);
                     }
-                    used[(size_t)t] = (size_t)(o - b.data());
-                });
-            }
-            for (auto &th : pool) th.join();
-            for (int t = 0; t < nt; ++t)
-                if (used[(size_t)t] && fwrite(bufs[(size_t)t].data(), 1, used[(size_t)t], fh) != used[(size_t)t])
+                    *o++ = '\n';
+                }
+                used[(size_t)slot] = (size_t)(o - b.data());
+            });
+            if (!done) throw std::bad_alloc();
+            for (int t = 0; t < n_blocks; ++t)
+                if (fwrite(bufs[(size_t)t].data(), 1, used[(size_t)t], fh) != used[(size_t)t])
                     rc = p2s_set_error(P2S_ERR_INVALID_ARG, "short write to %s", path);
         }
     } catch (const std::bad_alloc &) {
@@ -168,91 +164,64 @@ int p2s_write_openpose_files(const char *dir_paths, const int64_t *dir_offsets, 
             return p2s_set_error(P2S_ERR_INVALID_ARG, "output position %d names marker %d of %d", i, marker_index[i], n_markers);
     const int64_t n_files = (int64_t)n_cams * n_frames;
     if (n_files == 0) return P2S_OK;
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    if (nt < 1) nt = 1;
-    if (nt > 16) nt = 16;                                     // file writing: never more than 16 host threads
     const int64_t grain = 64;
-    if ((int64_t)nt > (n_files + grain - 1) / grain) nt = (int)((n_files + grain - 1) / grain);
+    const int nt = host_threads(n_threads, 16, (n_files + grain - 1) / grain);   // file writing: never more than 16 host threads
     static const char head[] = "{\"version\": 1.3, \"people\": [{\"person_id\": [-1], \"pose_keypoints_2d\": [";
     static const char tail[] = "], \"face_keypoints_2d\": [], \"hand_left_keypoints_2d\": [], \"hand_right_keypoints_2d\": [], "
                                "\"pose_keypoints_3d\": [], \"face_keypoints_3d\": [], \"hand_left_keypoints_3d\": [], "
                                "\"hand_right_keypoints_3d\": []}]}";
-    std::atomic<int64_t> next{0}, done{0}, first_bad{n_files};
+    std::atomic<int64_t> done{0}, first_bad{n_files};
     std::vector<int> errs((size_t)nt, 0);
     std::vector<std::string> bad_path((size_t)nt);
     std::vector<int64_t> bad_file((size_t)nt, n_files);
-    auto work_files = [&](int t) {
+    const bool all_run = parallel_for(n_files, nt, grain, [&](int t, int64_t lo, int64_t hi) {
         std::vector<char> buf(sizeof head + sizeof tail + (size_t)n_out * 64);
         std::string path;
         char num[32];
-        while (true) {
-            const int64_t b = next.fetch_add(grain);
-            if (b >= n_files) break;
-            const int64_t e = b + grain < n_files ? b + grain : n_files;
-            for (int64_t i = b; i < e; ++i) {
-                const int64_t c = i / n_frames, f = i % n_frames;
-                char *o = buf.data();
-                memcpy(o, head, sizeof head - 1);
-                o += sizeof head - 1;
-                const double *row = uv + (c * n_frames + f) * (int64_t)n_markers * 2;
-                for (int32_t k = 0; k < n_out; ++k) {
-                    const double x = row[2 * marker_index[k]], y = row[2 * marker_index[k] + 1];
-                    if (k) { *o++ = ','; *o++ = ' '; }
-                    if (x != x || y != y) {
-                        memcpy(o, "0.0, 0.0, 0", 11);
-                        o += 11;
-                    } else {
-                        o = py_repr(o, x);
-                        *o++ = ','; *o++ = ' ';
-                        o = py_repr(o, y);
-                        memcpy(o, ", 1", 3);
-                        o += 3;
-                    }
-                }
-                memcpy(o, tail, sizeof tail - 1);
-                o += sizeof tail - 1;
-                path.assign(dir_paths + dir_offsets[c], (size_t)(dir_offsets[c + 1] - dir_offsets[c]));
-                path += '/';
-                path += name_root;
-                snprintf(num, sizeof num, "_cam%02d_openpose_%04lld.json", (int)(c + 1), (long long)f);
-                path += num;
-                FILE *fh = fopen(path.c_str(), "wb");
-                const size_t n = (size_t)(o - buf.data());
-                bool ok = fh != nullptr;
-                int err = ok ? 0 : errno;
-                if (ok && fwrite(buf.data(), 1, n, fh) != n) { ok = false; err = errno; }
-                if (fh && fclose(fh) != 0 && ok) { ok = false; err = errno; }
-                if (ok) {
-                    done.fetch_add(1);
-                } else if (i < bad_file[(size_t)t]) {
-                    bad_file[(size_t)t] = i; errs[(size_t)t] = err; bad_path[(size_t)t] = path;
-                    int64_t cur = first_bad.load();
-                    while (i < cur && !first_bad.compare_exchange_weak(cur, i)) {}
+        for (int64_t i = lo; i < hi; ++i) {
+            const int64_t c = i / n_frames, f = i % n_frames;
+            char *o = buf.data();
+            memcpy(o, head, sizeof head - 1);
+            o += sizeof head - 1;
+            const double *row = uv + (c * n_frames + f) * (int64_t)n_markers * 2;
+            for (int32_t k = 0; k < n_out; ++k) {
+                const double x = row[2 * marker_index[k]], y = row[2 * marker_index[k] + 1];
+                if (k) { *o++ = ','; *o++ = ' '; }
+                if (x != x || y != y) {
+                    memcpy(o, "0.0, 0.0, 0", 11);
+                    o += 11;
+                } else {
+                    o = py_repr(o, x);
+                    *o++ = ','; *o++ = ' ';
+                    o = py_repr(o, y);
+                    memcpy(o, ", 1", 3);
+                    o += 3;
                 }
             }
+            memcpy(o, tail, sizeof tail - 1);
+            o += sizeof tail - 1;
+            path.assign(dir_paths + dir_offsets[c], (size_t)(dir_offsets[c + 1] - dir_offsets[c]));
+            path += '/';
+            path += name_root;
+            snprintf(num, sizeof num, "_cam%02d_openpose_%04lld.json", (int)(c + 1), (long long)f);
+            path += num;
+            FILE *fh = fopen(path.c_str(), "wb");
+            const size_t n = (size_t)(o - buf.data());
+            bool ok = fh != nullptr;
+            int err = ok ? 0 : errno;
+            if (ok && fwrite(buf.data(), 1, n, fh) != n) { ok = false; err = errno; }
+            if (fh && fclose(fh) != 0 && ok) { ok = false; err = errno; }
+            if (ok) {
+                done.fetch_add(1);
+            } else if (i < bad_file[(size_t)t]) {
+                bad_file[(size_t)t] = i; errs[(size_t)t] = err; bad_path[(size_t)t] = path;
+                int64_t cur = first_bad.load();
+                while (i < cur && !first_bad.compare_exchange_weak(cur, i)) {}
+            }
         }
-    };
-    std::atomic<bool> oom{false};
-    auto work = [&](int t) {
-        try {
-            work_files(t);
-        } catch (const std::bad_alloc &) {                    // on a pool thread: reported after the join, never thrown across it
-            oom.store(true);
-        }
-    };
-    try {
-        if (nt <= 1) {
-            work(0);
-        } else {
-            std::vector<std::thread> pool;
-            for (int t = 0; t < nt; ++t) pool.emplace_back(work, t);
-            for (auto &th : pool) th.join();
-        }
-    } catch (const std::bad_alloc &) {
-        return p2s_set_error(P2S_ERR_OOM, "out of host memory while formatting");
-    }
+    });
     if (n_written) *n_written = done.load();
-    if (oom.load()) return p2s_set_error(P2S_ERR_OOM, "out of host memory while formatting");
+    if (!all_run) return p2s_set_error(P2S_ERR_OOM, "out of host memory while formatting");
     const int64_t bad = first_bad.load();
     if (bad < n_files)
         for (int t = 0; t < nt; ++t)
