@@ -382,6 +382,52 @@ int p2s_id_switch_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, co
 /* Milliseconds the kernels of this context's last p2s_id_switch_host took (HIP events around them). */
 int p2s_id_switch_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
 
+/* ---- find_peaks (scipy.signal, 1.15.3) -----------------------------------------------------------------------------------
+ * scipy.signal.find_peaks(x, prominence=p) for each of n_cols contiguous float64 columns of n_rows entries (column-major,
+ * as p2s_column_order_stats_host takes them), bit for bit: _local_maxima_1d (a plateau's peak is (left_edge + right_edge)
+ * / 2, the first and last samples are never peaks, a comparison with NaN is false) and _peak_prominences with wlen=None
+ * (from the peak outwards while the samples are <= the peak -- a larger sample or a NaN ends the scan -- the smallest
+ * sample met and the position nearest to the peak that holds it; prominence = x[peak] - max(left_min, right_min), one
+ * subtraction).  prominence [n_cols]: a peak of column c is kept when prominence[c] <= its prominence, false for a NaN on
+ * either side, so +inf keeps none but a peak of infinite prominence; NULL keeps every local maximum (its prominence is still computed).
+ *   peaks, prominences, left_bases, right_bases [capacity]: the kept peaks of column 0 in ascending row order, then
+ *                  column 1's, ...; rows as indices into the column
+ *   col_counts [n_cols]  kept peaks per column
+ *   n_peaks        their total, whatever the capacity: when it exceeds capacity only the first capacity were written and
+ *                  the caller asks again with room for all.  capacity 0 only counts.
+ * 1 <= n_rows < 2^31, n_cols >= 1, n_rows * n_cols <= 2^36.  HOST pointers; blocks. */
+int p2s_find_peaks_host(p2s_ctx *ctx, int64_t n_rows, int32_t n_cols, const double *data, const double *prominence,
+                        int64_t capacity, int64_t *peaks, double *prominences, int64_t *left_bases,
+                        int64_t *right_bases, int32_t *col_counts, int64_t *n_peaks);
+
+/* ---- gait contact signals (Utilities/trc_gaitevents.py:387-576) ------------------------------------------------------------
+ * What gait_events_height_coords (method 0) and gait_events_fwd_vel (method 1) do to a toe column, for a batch of
+ * columns of unequal length at once.  data [max_rows][n_cols] row-major: column c holds col_len[c] samples (1 <=
+ * col_len[c] <= max_rows < 2^31), what follows them is never read.  With s = factor[c] * column:
+ *   method 0  signal = scipy.signal.filtfilt(b, a, s[1:]) over the whole column (odd extension by padlen = 3 n_coef,
+ *             lfilter_zi start): zeros are data, a NaN makes the column NaN.  b, a [n_coef] (a[0] = 1, 2 <= n_coef <= 9),
+ *             zi [n_coef - 1].  A column with col_len[c] - 1 <= padlen is refused with scipy's message.
+ *   method 1  v = diff(s) / dt[c]; v where it has the sign `sign` (1 or -1), else 0 (also for a NaN); abs; [1:];
+ *             signal = scipy.ndimage.correlate1d(., weights, mode='reflect') with the n_weights = 2 radius + 1 weights of
+ *             gaussian_filter1d.
+ * signal [max_rows - 1][n_cols] row-major: col_len[c] - 1 samples per column, within 1e-9 relative of scipy's.  Then
+ * low = signal < threshold[c] and start_end_true_seq (:116-133):
+ *   on  [n_cols][event_capacity]  the samples i >= 1 with low[i] and not low[i - 1], ascending (index 0 is taken off,
+ *                                 as the callers of start_end_true_seq do)
+ *   off [n_cols][event_capacity]  i - 1 for the samples i >= 1 with low[i - 1] and not low[i] (the reference's -1 is dropped)
+ *   n_on, n_off [n_cols]          how many there are, whatever the capacity: when one exceeds event_capacity only the
+ *                                 first event_capacity of that column were written and the caller asks again with room
+ *   first_low [n_cols]            low[0]: with n_off = 0 it tells an all-true signal, on which start_end_true_seq raises
+ * signal, on and off may be NULL (on and off only with event_capacity 0).  HOST pointers; blocks. */
+int p2s_gait_contacts_host(p2s_ctx *ctx, int32_t method, int32_t n_cols, int64_t max_rows, const int64_t *col_len,
+                           const double *data, const double *dt, const double *threshold, const double *factor,
+                           int32_t sign, int32_t n_coef, const double *b, const double *a, const double *zi,
+                           int32_t n_weights, const double *weights, double *signal, int64_t event_capacity, int32_t *on,
+                           int32_t *off, int32_t *n_on, int32_t *n_off, uint8_t *first_low);
+/* Milliseconds the kernels of this context's last p2s_find_peaks_host or p2s_gait_contacts_host took (HIP events around
+ * them). */
+int p2s_gait_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
+
 /* ---- synchronization (synchronize_cams_all, synchronization.py:1346-1612) ------------------------------------------
  * Speeds: replaces the per-camera pandas / scipy work of :1562-1584 (interpolate_zeros_nans :1565, bfill().ffill(),
  * signal.filtfilt :1568, vert_speed :1271-1288, abs().sum(axis=1) :1579, filtfilt of the sum :1585).  coords: the cameras'

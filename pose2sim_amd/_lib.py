@@ -105,6 +105,12 @@ SIGNATURES = {
     'p2s_lsap_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
     'p2s_id_switch_host': (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 8),
     'p2s_id_switch_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    'p2s_find_peaks_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]
+                            + [C.c_void_p] * 5 + [C.POINTER(C.c_int64)]),
+    'p2s_gait_contacts_host': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 5
+                               + [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]
+                               + [C.c_void_p] * 5),
+    'p2s_gait_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     'p2s_json_person_ids': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'p2s_timing_begin': (C.c_int, [C.c_void_p]),
     'p2s_timing_end': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
@@ -134,7 +140,8 @@ OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_h
             'p2s_copy_files', 'p2s_reproject_host', 'p2s_reproject_kernel_ms', 'p2s_write_openpose_files',
             'p2s_column_order_stats_host', 'p2s_jitter_host', 'p2s_jitter_kernel_ms', 'p2s_json_select_tracked_person',
             'p2s_column_mean_std_host', 'p2s_confidence_stats_host', 'p2s_confidence_kernel_ms', 'p2s_lsap_host',
-            'p2s_id_switch_host', 'p2s_id_switch_kernel_ms', 'p2s_json_person_ids', 'p2s_loess_host'}
+            'p2s_id_switch_host', 'p2s_id_switch_kernel_ms', 'p2s_json_person_ids', 'p2s_loess_host',
+            'p2s_find_peaks_host', 'p2s_gait_contacts_host', 'p2s_gait_kernel_ms'}
 
 _lib = None
 

@@ -437,6 +437,92 @@ class Engine:
         _lib.check(fn(self._h, C.byref(ms)))
         return ms.value
 
+    # -- scipy.signal.find_peaks; gait contact signals (Utilities/trc_gaitevents.py) ---------------------------------------
+    def find_peaks(self, data, prominence=None):
+        """scipy.signal.find_peaks(column, prominence=prominence) for every column of data [n_rows][n_cols] float64 (any
+        strides), bit for bit; prominence: one bound, or one per column.  -> one (peaks int64, prominences, left_bases
+        int64, right_bases int64) per column.  With prominence None every local maximum is returned, with its prominence
+        and bases."""
+        fn = _entry(self._lib, 'p2s_find_peaks_host')
+        data = np.asarray(data, dtype=np.float64)
+        if data.ndim != 2 or data.shape[0] < 1 or data.shape[1] < 1:
+            raise P2sError(f'data has shape {data.shape}; expected [n_rows >= 1][n_cols >= 1]')
+        cols = np.ascontiguousarray(data.T)                       # the library takes the columns contiguous
+        n_cols, n_rows = cols.shape
+        bound = None if prominence is None else np.ascontiguousarray(np.broadcast_to(np.asarray(prominence, dtype=np.float64), (n_cols,)))
+        capacity = min(max(cols.size // 16, 64), 1 << 22)
+        counts, found = np.zeros(n_cols, dtype=np.int32), C.c_int64(0)
+        while True:
+            peaks, lb, rb = (np.empty(capacity, dtype=np.int64) for _ in range(3))
+            prom = np.empty(capacity)
+            _lib.check(fn(self._h, n_rows, n_cols, _ptr(cols), _ptr(bound), capacity, _ptr(peaks), _ptr(prom), _ptr(lb), _ptr(rb),
+                          _ptr(counts), C.byref(found)))
+            if found.value <= capacity:
+                break
+            capacity = found.value                                # a second call with room for every peak
+        off = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+        return [(peaks[off[c]:off[c + 1]], prom[off[c]:off[c + 1]], lb[off[c]:off[c + 1]], rb[off[c]:off[c + 1]]) for c in range(n_cols)]
+
+    GAIT_METHODS = {'height_coordinates': 0, 'forward_velocity': 1}
+
+    def gait_contacts(self, columns, method, dt, threshold, factor=1.0, sign=1, b=None, a=None, zi=None, weights=None):
+        """The contact signal of trc_gaitevents' two threshold methods and its runs, for a batch of toe columns at once.
+        columns: 1-D float64 arrays, lengths may differ; dt, threshold, factor: one value or one per column.
+        'height_coordinates': scipy.signal.filtfilt(b, a, (factor * column)[1:]) over the whole column, zi =
+        lfilter_zi(b, a); a column too short for its padding raises scipy's ValueError.  'forward_velocity': diff / dt,
+        the samples whose sign is not `sign` zeroed, abs, [1:], correlate1d with `weights` (gaussian_filter1d's, from the
+        host), mode 'reflect'.  -> (signals, on, off, first_low): per column the filtered signal (one sample fewer than
+        the column), the run starts of signal < threshold with index 0 taken off, the run ends, and whether the first
+        sample is below the threshold (with no run end: start_end_true_seq raises on such a column)."""
+        fn = _entry(self._lib, 'p2s_gait_contacts_host')
+        if method not in self.GAIT_METHODS:
+            raise P2sError(f'method {method!r}; expected one of {sorted(self.GAIT_METHODS)}')
+        m = self.GAIT_METHODS[method]
+        columns = [np.asarray(c, dtype=np.float64).reshape(-1) for c in columns]
+        n = len(columns)
+        if n < 1 or min(len(c) for c in columns) < 1:
+            raise P2sError('gait_contacts: at least one column, every column with at least one sample')
+        lens = np.array([len(c) for c in columns], dtype=np.int64)
+        max_rows = int(lens.max())
+        per_col = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)))   # noqa: E731
+        dt, threshold, factor = per_col(dt), per_col(threshold), per_col(factor)
+        n_coef = n_w = 0
+        if m == 0:
+            b, a, zi = (np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (b, a, zi))
+            if len(a) != len(b) or len(zi) != len(b) - 1:
+                raise P2sError('b, a and zi must have n, n and n - 1 coefficients')
+            n_coef = len(b)
+            if int(lens.min()) - 1 <= 3 * n_coef:                 # scipy.signal.filtfilt's own refusal (_validate_pad)
+                raise ValueError(f'The length of the input vector x must be greater than padlen, which is {3 * n_coef}.')
+        else:
+            weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            n_w = len(weights)
+        table = np.full((max_rows, n), np.nan)
+        for c, col in enumerate(columns):
+            table[:len(col), c] = col
+        signal = np.empty((max_rows - 1, n))
+        n_on, n_off, first = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint8)
+        capacity = 256
+        while True:
+            on, off = np.empty((n, capacity), dtype=np.int32), np.empty((n, capacity), dtype=np.int32)
+            _lib.check(fn(self._h, m, n, max_rows, _ptr(lens), _ptr(table), _ptr(dt), _ptr(threshold), _ptr(factor), int(sign),
+                          n_coef, _ptr(b) if m == 0 else None, _ptr(a) if m == 0 else None, _ptr(zi) if m == 0 else None,
+                          n_w, _ptr(weights) if m == 1 else None, _optr(signal), capacity, _ptr(on), _ptr(off), _ptr(n_on),
+                          _ptr(n_off), _ptr(first)))
+            need = int(max(n_on.max(), n_off.max()))
+            if need <= capacity:
+                break
+            capacity = need                                       # a second call with room for every event
+        return ([signal[:lens[c] - 1, c] for c in range(n)], [on[c, :n_on[c]].astype(np.int64) for c in range(n)],
+                [off[c, :n_off[c]].astype(np.int64) for c in range(n)], first.astype(bool))
+
+    def gait_kernel_ms(self):
+        """Kernel time of the last find_peaks() or gait_contacts() call, from HIP events around its kernels."""
+        fn = _entry(self._lib, 'p2s_gait_kernel_ms')
+        ms = C.c_float(0)
+        _lib.check(fn(self._h, C.byref(ms)))
+        return ms.value
+
     # -- np.mean / np.std of columns; 2D confidence statistics (Utilities/pose_confidence_analyze.py:118-219) ------------
     def column_mean_std(self, data):
         """data [n_rows][n_cols] float64 (any strides; NaN entries are skipped).  -> (mean [n_cols], std [n_cols], counts
