@@ -2,7 +2,7 @@
 
 The pooled triangulation kernel's fp32 screen (p2s_tri_pool.hip, tier A) was tuned on one rig family -- a ring at 4-6 m,
 f ~ 1400 px, 1920 x 1080 -- and on likelihoods of 0.3 or more.  This module builds the other geometries and likelihood
-patterns the screen has to survive, as pinhole calibrations (dist = 0) in the dict form synth.make_cameras returns:
+patterns the kernels have to survive, as pinhole calibrations (dist = 0) in the dict form synth.make_cameras returns:
 
 rig families (RIGS)
   ring        synth.make_cameras itself, the control
@@ -21,6 +21,21 @@ likelihood modes (LIK_MODES)
   heavy_light per unit 1-2 cameras at likelihood 1.0 with gross outliers, the others accurate at 1e-3 .. 1e-2: every
               level-1 and level-2 candidate is then a large downdate of the level-0 normal matrix
 
+distortion profiles (DISTORTIONS; `distortion=` of make_rig and make_workload, default 'none' = the pinhole rigs above)
+  mild5       synth.make_cameras' ranges (|k1| <= 0.1, |k2| <= 0.05, |p| <= 1e-3) and k3 in +-0.02
+  wide        an action-camera lens: f = 0.5 x sensor width (the corner at r^2 ~ 1.2-1.4), k1 in [-0.32, -0.25], k2 in
+              [0.06, 0.12], k3 in [-0.02, -0.005], |p| <= 2e-3, drawn until r cdist(r) rises all the way to the image corner.
+              The five fixed-point iterations of the undistortion do not converge near the edge of such a lens; 1 % of the
+              observations are moved to uniformly random pixels so that some lie there
+  pincushion  k1 in [0.1, 0.25], k2 in [0, 0.05], FOUR terms (the len(dist) == 4 packing)
+  runaway     f = 0.47 x sensor width, k1 and k2 mild and a k3 of -0.6 .. -1.0 that takes 1 + k1 r^2 + k2 r^4 + k3 r^6 through
+              zero inside the image, 900-970 px from the principal point at 1920 x 1080 (corner: 1100 px); 3 % of the
+              observations are moved to uniformly random pixels, and those beyond the zero, or whose iterates cross it,
+              leave the undistortion through its `icdist < 0` exit (fallback_counts)
+Every lens is laid out on its camera's own sensor size (cams['S']), so the uhd, stadium and mixed families distort at their
+own resolutions.  With a profile the observations are projected through the distorted model, cams['optim_K'] is
+cvmath.get_optimal_new_camera_matrix of the lens and P is built on it, as the reference does with undistort_points.
+
 `dup=True` makes camera 1 a copy of camera 0 (P and observations): two candidates of a level then have bit-equal fp64
 errors and the rank decides (np.nanargmin's first index).
 """
@@ -30,6 +45,7 @@ from pose2sim_amd import cvmath, synth
 
 RIGS = ('ring', 'uhd', 'far_origin', 'stadium', 'close', 'one_side', 'overhead', 'mixed')
 LIK_MODES = ('clamped', 'low', 'zeros', 'heavy_light')
+DISTORTIONS = ('none', 'mild5', 'wide', 'pincushion', 'runaway')
 
 
 def _camera(cams, name, pos, target, f, width, height, rng):
@@ -75,8 +91,10 @@ def scene(family):
     return np.ones(3), np.zeros(3)
 
 
-def make_rig(family, C, seed=0):
-    """C pinhole cameras of one family, in synth.make_cameras' dict form."""
+def make_rig(family, C, seed=0, distortion='none'):
+    """C cameras of one family, in synth.make_cameras' dict form: pinhole, or with the lenses of a distortion profile."""
+    if distortion != 'none':
+        return _distort(make_rig(family, C, seed), distortion, seed)
     if family == 'ring':
         return synth.make_cameras(C, seed=seed)
     rng = np.random.default_rng(seed + 7919)
@@ -125,14 +143,137 @@ def make_rig(family, C, seed=0):
     return cams
 
 
+def radial(dist, r2):
+    """1 + k1 r^2 + k2 r^4 + k3 r^6 of a 4- or 5-term OpenCV distortion vector (k1, k2, p1, p2[, k3])."""
+    d = np.asarray(dist, dtype=np.float64)
+    k3 = d[4] if len(d) > 4 else 0.0
+    return 1 + ((k3 * r2 + d[1]) * r2 + d[0]) * r2
+
+
+def corner_radius(K, size):
+    """The largest distance (normalised, distorted coordinates) from the principal point to an image corner."""
+    w, h = float(size[0]), float(size[1])
+    return max(np.hypot((x - K[0, 2]) / K[0, 0], (y - K[1, 2]) / K[1, 1]) for x in (0.0, w - 1) for y in (0.0, h - 1))
+
+
+def forward_slope_to_corner(K, dist, size, n=4000):
+    """(min d(r cdist(r))/dr over the ideal radii whose image lies inside the sensor, ideal radius of the corner).  The radial
+    forward model r -> r cdist(r) is walked outwards on a grid until it reaches the corner; the ideal radius comes back as
+    None when it turns back before it gets there."""
+    d = np.asarray(dist, dtype=np.float64)
+    k3 = d[4] if len(d) > 4 else 0.0
+    rc = corner_radius(K, size)
+    r = np.linspace(0.0, 4.0 * rc + 1.0, n)
+    slope = 1 + 3 * d[0] * r ** 2 + 5 * d[1] * r ** 4 + 7 * k3 * r ** 6
+    reach = np.flatnonzero(r * radial(d, r * r) >= rc)
+    turn = np.flatnonzero(slope <= 0)
+    if reach.size == 0 or (turn.size and turn[0] <= reach[0]):
+        return float(slope[:(turn[0] + 1) if turn.size else n].min()), None
+    return float(slope[:reach[0] + 1].min()), float(r[reach[0]])
+
+
+def _coefficients(profile, K, size, rng):
+    """One lens of a profile (the table in the module's header)."""
+    if profile == 'mild5':
+        return np.array([rng.uniform(-0.1, 0.1), rng.uniform(-0.05, 0.05), rng.uniform(-1e-3, 1e-3), rng.uniform(-1e-3, 1e-3),
+                         rng.uniform(-0.02, 0.02)])
+    if profile == 'pincushion':
+        return np.array([rng.uniform(0.1, 0.25), rng.uniform(0.0, 0.05), rng.uniform(-1e-3, 1e-3), rng.uniform(-1e-3, 1e-3)])
+    if profile == 'runaway':
+        # k1, k2 as mild as synth's and a k3 that takes 1 + k1 r^2 + k2 r^4 + k3 r^6 through zero at r^2 = 1.0 .. 1.15 (900 - 970 px
+        # from the principal point of a 1920 x 1080 sensor, whose corner is at 1100 px).  Past the fold of the forward model the
+        # fixed-point iteration has nowhere to converge to, and a non-converged iterate on the 9 x 9 grid of
+        # getOptimalNewCameraMatrix can stretch optim_K to half of K; the reference's error with undistortion (undistorted
+        # observation against the reprojection through K and dist, quirk Q4) is then hundreds of px for every unit and nothing
+        # is triangulated.  Lenses are drawn until optim_K stays within 8 % (focal lengths) and 1.5 % of the sensor width
+        # (principal point) of K: the error of a unit in mid-image is then about 10 px.
+        for _ in range(1000):
+            k1, k2, s = rng.uniform(-0.1, 0.1), rng.uniform(0.0, 0.05), rng.uniform(1.0, 1.15)
+            d = np.array([k1, k2, rng.uniform(-1e-3, 1e-3), rng.uniform(-1e-3, 1e-3), -(1 + k1 * s + k2 * s * s) / s ** 3])
+            nK = cvmath.get_optimal_new_camera_matrix(K, d, size, 1.0)
+            if (abs(nK[0, 0] / K[0, 0] - 1) < 0.08 and abs(nK[1, 1] / K[1, 1] - 1) < 0.08
+                    and abs(nK[0, 2] - K[0, 2]) < 0.015 * size[0] and abs(nK[1, 2] - K[1, 2]) < 0.015 * size[0]):
+                return d
+        raise RuntimeError('no runaway lens with a usable optim_K in 1000 draws')
+    if profile == 'wide':
+        for _ in range(1000):              # the ranges hold lenses that fold back inside the image: draw until one does not
+            d = np.array([rng.uniform(-0.32, -0.25), rng.uniform(0.06, 0.12), rng.uniform(-2e-3, 2e-3), rng.uniform(-2e-3, 2e-3),
+                          rng.uniform(-0.02, -0.005)])
+            slope, r_corner = forward_slope_to_corner(K, d, size)
+            if r_corner is not None and slope > 0.02:
+                return d
+        raise RuntimeError('no monotone wide lens in 1000 draws')
+    raise ValueError(f'unknown distortion profile {profile!r}')
+
+
+def _distort(cams, profile, seed):
+    """Gives every camera of a pinhole rig a lens of `profile`, at the camera's own sensor size: `wide` and `runaway` also
+    set the focal length (0.5 x and 0.47 x the sensor width); dist, optim_K and inv_K follow."""
+    rng = np.random.default_rng(seed + 104729)
+    for c in range(len(cams['K'])):
+        width, height = (int(s) for s in cams['S'][c])
+        K = np.array(cams['K'][c], dtype=np.float64)
+        if profile in ('wide', 'runaway'):
+            f = (0.5 if profile == 'wide' else 0.47) * width * (1 + rng.uniform(-0.03, 0.03))
+            K[1, 1] *= f / K[0, 0]
+            K[0, 0] = f
+        d = _coefficients(profile, K, (width, height), rng)
+        cams['K'][c] = K
+        cams['dist'][c] = d
+        cams['optim_K'][c] = cvmath.get_optimal_new_camera_matrix(K, d, (width, height), 1.0)
+        cams['inv_K'][c] = np.linalg.inv(K)
+    return cams
+
+
+def fallback_counts(xyl, cams):
+    """(first, later): the observations with finite coordinates whose undistortion (cv2.undistortPoints' five fixed-point
+    iterations, pose2sim_amd/cvmath.py) leaves through the `icdist < 0` exit at the first iteration, and at a later one."""
+    x = np.asarray(xyl)
+    x = x.reshape((-1,) + x.shape[-3:])
+    first = later = 0
+    for c in range(x.shape[1]):
+        K, d = np.asarray(cams['K'][c], dtype=np.float64), np.zeros(5)
+        dc = np.asarray(cams['dist'][c], dtype=np.float64).ravel()
+        d[:len(dc)] = dc
+        u = x[:, c, :, 0].astype(np.float32).astype(np.float64).ravel()
+        v = x[:, c, :, 1].astype(np.float32).astype(np.float64).ravel()
+        fin = np.isfinite(u) & np.isfinite(v)
+        x0, y0 = (u[fin] - K[0, 2]) * (1.0 / K[0, 0]), (v[fin] - K[1, 2]) * (1.0 / K[1, 1])
+        px, py = x0.copy(), y0.copy()
+        live = np.ones(px.shape, dtype=bool)
+        for j in range(5):
+            r2 = px * px + py * py
+            with np.errstate(all='ignore'):
+                icdist = 1.0 / (1 + ((d[4] * r2 + d[1]) * r2 + d[0]) * r2)
+                out = live & (icdist < 0)
+                dx = 2 * d[2] * px * py + d[3] * (r2 + 2 * px * px)
+                dy = d[2] * (r2 + 2 * py * py) + 2 * d[3] * px * py
+                nx, ny = (x0 - dx) * icdist, (y0 - dy) * icdist
+            if j == 0:
+                first += int(out.sum())
+            else:
+                later += int(out.sum())
+            live &= ~out
+            px, py = np.where(live, nx, px), np.where(live, ny, py)
+    return first, later
+
+
 def _duplicate_camera0(cams):
     for k in cams:
         cams[k][1] = cams[k][0].copy() if hasattr(cams[k][0], 'copy') else cams[k][0]
 
 
-def make_workload(family, C, F, K=26, lik='clamped', seed=0, dup=False, p_outlier=0.06, noise_px=1.5):
-    """One workload: dict(xyl float32 [F][1][C][K][3], cams, P, Q3d) on a rig of `family` with likelihood mode `lik`."""
-    cams = make_rig(family, C, seed)
+# share of the observations moved to uniformly random pixels of their sensor
+SCATTER = {'none': 0.0, 'mild5': 0.0, 'wide': 0.01, 'pincushion': 0.0, 'runaway': 0.03}
+
+
+def make_workload(family, C, F, K=26, lik='clamped', seed=0, dup=False, p_outlier=0.06, noise_px=1.5, distortion='none',
+                  p_lr_swap=0.0, swap_idx=None):
+    """One workload: dict(xyl float32 [F][1][C][K][3], cams, P, Q3d) on a rig of `family` with likelihood mode `lik`.  With a
+    distortion profile the observations go through the distorted camera model, P is built on optim_K (the undistorted
+    image), and SCATTER[distortion] of the observations move to uniformly random pixels of their sensor."""
+    cams = make_rig(family, C, seed, distortion)
+    distort = distortion != 'none'
     if dup:
         _duplicate_camera0(cams)
     scale, offset = scene(family)
@@ -141,7 +282,8 @@ def make_workload(family, C, F, K=26, lik='clamped', seed=0, dup=False, p_outlie
         Q3d[..., 0] += (5.0 * (np.arange(F) % 97) / 96.0 - 2.5)[:, None, None]
     rng = np.random.default_rng(seed + 31337)
     if lik == 'heavy_light':
-        xyl = synth.make_observations(Q3d, cams, seed=seed, noise_px=noise_px, p_lowlik=0.0, p_outlier=0.0, p_missing_cam=0.0)
+        xyl = synth.make_observations(Q3d, cams, seed=seed, noise_px=noise_px, p_lowlik=0.0, p_outlier=0.0, p_missing_cam=0.0,
+                                      distort=distort)
         u = xyl[:, 0]                                             # [F][C][K][3] view
         lw = np.exp(rng.uniform(np.log(1e-3), np.log(1e-2), (F, C, K)))
         n_heavy = 1 + (rng.random((F, K)) < 0.5)
@@ -154,7 +296,8 @@ def make_workload(family, C, F, K=26, lik='clamped', seed=0, dup=False, p_outlie
         u[..., 1] = np.where(heavy, u[..., 1] + mag * np.sin(ang), u[..., 1])
         u[..., 2] = np.where(heavy, 1.0, lw)
     else:
-        xyl = synth.make_observations(Q3d, cams, seed=seed, noise_px=noise_px, p_outlier=p_outlier)
+        xyl = synth.make_observations(Q3d, cams, seed=seed, noise_px=noise_px, p_outlier=p_outlier, distort=distort,
+                                      p_lr_swap=p_lr_swap, swap_idx=swap_idx)
         u = xyl[:, 0]
         if lik == 'low':
             low = rng.random((F, C, K)) < 0.5
@@ -164,6 +307,14 @@ def make_workload(family, C, F, K=26, lik='clamped', seed=0, dup=False, p_outlie
             u[z] = 0.0
         elif lik != 'clamped':
             raise ValueError(f'unknown likelihood mode {lik!r}')
+    if distort and SCATTER[distortion] > 0:
+        srng = np.random.default_rng(seed + 15485863)
+        u = xyl[:, 0]
+        for c in range(C):
+            move = (srng.random((F, K)) < SCATTER[distortion]) & np.isfinite(u[:, c, :, 0])
+            u[:, c, :, 0] = np.where(move, srng.uniform(0.0, cams['S'][c][0] - 1, (F, K)), u[:, c, :, 0])
+            u[:, c, :, 1] = np.where(move, srng.uniform(0.0, cams['S'][c][1] - 1, (F, K)), u[:, c, :, 1])
     if dup:
         xyl[:, :, 1] = xyl[:, :, 0]
-    return {'xyl': np.ascontiguousarray(xyl, dtype=np.float32), 'cams': cams, 'P': synth.projection_matrices(cams), 'Q3d': Q3d}
+    return {'xyl': np.ascontiguousarray(xyl, dtype=np.float32), 'cams': cams, 'P': synth.projection_matrices(cams, undistort=distort),
+            'Q3d': Q3d}
