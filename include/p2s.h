@@ -428,6 +428,55 @@ int p2s_gait_contacts_host(p2s_ctx *ctx, int32_t method, int32_t n_cols, int64_t
  * them). */
 int p2s_gait_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
 
+/* ---- body measurements from .trc tables (common.py:378-455, :715-1034; kinematics.py:278-304) ------------------------
+ * The stable order of n_segments columns of float64 keys, data back to back, seg_len[s] entries each (1 .. 2^31 - 1):
+ * order [sum seg_len] = np.argsort(column, kind='stable') per column -- -inf < ... < -0.0 = +0.0 < ... < inf < NaN, equal
+ * keys in input order. */
+int p2s_stable_argsort_host(p2s_ctx *ctx, int64_t n_segments, const int64_t *seg_len, const double *data, int32_t *order);
+/* trimmed_mean (common.py:427-455) of every column, bit for bit: np.mean(np.sort(x)[int(n * half_trim) :
+ * int(n * (1 - half_trim))]), np.mean(x) when that slice is empty; half_trim = trimmed_extrema_percent / 2 in [0, 0.5]. */
+int p2s_trimmed_means_host(p2s_ctx *ctx, int64_t n_segments, const int64_t *seg_len, const double *data, double half_trim,
+                           double *means);
+/* best_coords_for_measurements, mean_angles, compute_height, compute_leg_length and the trimmed segment lengths of
+ * dict_segment_ratio for n_files tables of unequal length in one call; no count comes back to the host between the steps.
+ * data: the tables back to back, [n_rows[f]][3 n_markers[f]].  Per file:
+ *   flags     P2S_MEASURE_SPEED     keep the frames whose summed speed is above speed_threshold[f], int(count *
+ *                                   keep_fraction) of them by ascending speed (every frame in file order when none is above)
+ *             P2S_MEASURE_ANGLES    mean_angles of the selected rows
+ *             P2S_MEASURE_RESTRICT  keep the rows with angle < angle_limit; fewer than 50: the first 50 rows by angle, NaN last
+ *             P2S_MEASURE_HEIGHT    row heights from pairs 0 .. 8; P2S_MEASURE_FEET_CONST: both feet are 0.10
+ *             P2S_MEASURE_LEG       row leg lengths from pairs 2 .. 5
+ *   roles     [10] marker indices of RShoulder LShoulder RHip LHip Hip Neck RKnee LKnee RAnkle LAnkle, -1 = not in the
+ *             file (Hip: the mid-hip, Neck: the mid-shoulder stand in)
+ *   pairs     [n_pairs][2] marker indices; n_markers[f] is the mid-shoulder, n_markers[f] + 1 the mid-hip, a pair with
+ *             a -1 is skipped (its lengths are 0).  Pairs 0 .. 8 of compute_height: heel-ankle R, L; ankle-knee R, L;
+ *             knee-hip R, L; hip-shoulder R, L; mid-shoulder to Head or Nose, times head_factor[f]
+ *   n_speed_markers  (may be NULL: every marker) the summed speed runs over the file's first n_speed_markers[f] markers
+ * When no row is left every frame of the file is kept.  At most 2^21 files (or segments, in the two calls above) and 2^33
+ * rows a call.  angles of a file without P2S_MEASURE_ANGLES are NaN.  Outputs (those marked * may be NULL), rows of all files back to
+ * back: sum_speeds* and angles* (the first n_selected[f] of a file), kept_pos and kept_frame (the first n_kept[f]: the
+ * row's place among the selected rows, which is the reference's index label, and its frame), branch (P2S_MEASURE_ALL_SLOW,
+ * _FEW_SMALL_ANGLES, _ALL_DATA), row_heights*, row_values* [n_pairs + 2][rows] (lengths per pair, heights, leg lengths),
+ * means [n_files][n_pairs + 2]: their trimmed means with half_trim as above. */
+#define P2S_MEASURE_SPEED 1
+#define P2S_MEASURE_ANGLES 2
+#define P2S_MEASURE_RESTRICT 4
+#define P2S_MEASURE_FEET_CONST 8
+#define P2S_MEASURE_HEIGHT 16
+#define P2S_MEASURE_LEG 32
+#define P2S_MEASURE_FLAGS 63
+#define P2S_MEASURE_ALL_SLOW 1
+#define P2S_MEASURE_FEW_SMALL_ANGLES 2
+#define P2S_MEASURE_ALL_DATA 4
+int p2s_body_measure_host(p2s_ctx *ctx, int32_t n_files, const int64_t *n_rows, const int32_t *n_markers, const double *data,
+                          const int32_t *flags, const int32_t *roles, int32_t n_pairs, const int32_t *pairs,
+                          const double *head_factor, const double *speed_threshold, const int32_t *n_speed_markers, double keep_fraction,
+                          double angle_limit, double half_trim, double *sum_speeds, double *angles, int32_t *n_selected, int32_t *kept_pos,
+                          int32_t *kept_frame, int32_t *n_kept, int32_t *branch, double *row_heights, double *row_values,
+                          double *means);
+/* Milliseconds the kernels of this context's last call of one of the three above took (HIP events around them). */
+int p2s_measure_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
+
 /* ---- synchronization (synchronize_cams_all, synchronization.py:1346-1612) ------------------------------------------
  * Speeds: replaces the per-camera pandas / scipy work of :1562-1584 (interpolate_zeros_nans :1565, bfill().ffill(),
  * signal.filtfilt :1568, vert_speed :1271-1288, abs().sum(axis=1) :1579, filtfilt of the sum :1585).  coords: the cameras'

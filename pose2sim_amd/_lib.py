@@ -27,6 +27,9 @@ P2S_ERR_SYNC_PADLEN = -10
 P2S_REPROJ_DISTORTED = 1
 P2S_TRACK_SELECTED, P2S_TRACK_NO_PEOPLE, P2S_TRACK_NO_CANDIDATE = 1, 0, 2
 P2S_TRACK_LONG_LIST, P2S_TRACK_BAD_FILE, P2S_TRACK_BAD_CONTENT = -1, -2, -3
+P2S_MEASURE_SPEED, P2S_MEASURE_ANGLES, P2S_MEASURE_RESTRICT, P2S_MEASURE_FEET_CONST, P2S_MEASURE_HEIGHT, P2S_MEASURE_LEG = 1, 2, 4, 8, 16, 32
+P2S_MEASURE_ALL_SLOW, P2S_MEASURE_FEW_SMALL_ANGLES, P2S_MEASURE_ALL_DATA = 1, 2, 4
+P2S_MEASURE_ROLES = ('RShoulder', 'LShoulder', 'RHip', 'LHip', 'Hip', 'Neck', 'RKnee', 'LKnee', 'RAnkle', 'LAnkle')
 
 
 class TriParams(C.Structure):
@@ -111,6 +114,11 @@ SIGNATURES = {
                                + [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]
                                + [C.c_void_p] * 5),
     'p2s_gait_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    'p2s_stable_argsort_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'p2s_trimmed_means_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    'p2s_body_measure_host': (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 4
+                              + [C.c_double] * 3 + [C.c_void_p] * 10),
+    'p2s_measure_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     'p2s_json_person_ids': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'p2s_timing_begin': (C.c_int, [C.c_void_p]),
     'p2s_timing_end': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
@@ -141,7 +149,8 @@ OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_h
             'p2s_column_order_stats_host', 'p2s_jitter_host', 'p2s_jitter_kernel_ms', 'p2s_json_select_tracked_person',
             'p2s_column_mean_std_host', 'p2s_confidence_stats_host', 'p2s_confidence_kernel_ms', 'p2s_lsap_host',
             'p2s_id_switch_host', 'p2s_id_switch_kernel_ms', 'p2s_json_person_ids', 'p2s_loess_host',
-            'p2s_find_peaks_host', 'p2s_gait_contacts_host', 'p2s_gait_kernel_ms'}
+            'p2s_find_peaks_host', 'p2s_gait_contacts_host', 'p2s_gait_kernel_ms', 'p2s_stable_argsort_host',
+            'p2s_trimmed_means_host', 'p2s_body_measure_host', 'p2s_measure_kernel_ms'}
 
 _lib = None
 

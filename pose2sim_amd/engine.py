@@ -523,6 +523,98 @@ class Engine:
         _lib.check(fn(self._h, C.byref(ms)))
         return ms.value
 
+    # -- stable sort, trimmed means, body measurements (common.py:378-455, :715-1034) ---------------------------------------
+    @staticmethod
+    def _segments(columns, what):
+        columns = [np.asarray(c, dtype=np.float64).reshape(-1) for c in columns]
+        if not columns or min(len(c) for c in columns) < 1:
+            raise P2sError(f'{what}: at least one column, every column with at least one entry')
+        return columns, np.array([len(c) for c in columns], dtype=np.int64), np.ascontiguousarray(np.concatenate(columns))
+
+    def stable_argsort(self, columns):
+        """columns: 1-D float64 arrays, lengths may differ.  -> one int64 order per column, np.argsort(column, kind='stable'):
+        -inf < ... < -0.0 = +0.0 < ... < inf < NaN, equal keys in input order.  One device call for the batch."""
+        fn = _entry(self._lib, 'p2s_stable_argsort_host')
+        columns, lens, data = self._segments(columns, 'stable_argsort')
+        order = np.empty(len(data), dtype=np.int32)
+        _lib.check(fn(self._h, len(columns), _ptr(lens), _ptr(data), _ptr(order)))
+        off = np.concatenate([[0], np.cumsum(lens)])
+        return [order[off[c]:off[c + 1]].astype(np.int64) for c in range(len(columns))]
+
+    def trimmed_means(self, columns, trimmed_extrema_percent=0.5):
+        """The reference's trimmed_mean (common.py:427-455) of every column, bit for bit: np.mean(np.sort(x)[int(n * p / 2) :
+        int(n * (1 - p / 2))]), np.mean(x) when the slice is empty.  columns: 1-D float64 arrays, lengths may differ.
+        -> float64 [n_columns]."""
+        fn = _entry(self._lib, 'p2s_trimmed_means_host')
+        columns, lens, data = self._segments(columns, 'trimmed_means')
+        means = np.empty(len(columns))
+        _lib.check(fn(self._h, len(columns), _ptr(lens), _ptr(data), float(trimmed_extrema_percent) / 2, _ptr(means)))
+        return means
+
+    def body_measure(self, tables, marker_index, pairs, flags, close_to_zero_speed=0.2, fastest_frames_to_remove_percent=0.2,
+                     large_hip_knee_angles=45, trimmed_extrema_percent=0.5, head_factor=1.008, row_values=False, n_speed_markers=None):
+        """best_coords_for_measurements, mean_angles, compute_height, compute_leg_length and trimmed segment lengths
+        (common.py:797-1034, kinematics.py:299-304) for a batch of tables in one device call.
+        tables: [n_rows][3 n_markers] float64 per file, shapes may differ.  marker_index: per file the 10 marker indices
+        of _lib.P2S_MEASURE_ROLES, -1 = absent.  pairs: per file [n_pairs][2] marker indices (n_markers = mid-shoulder,
+        n_markers + 1 = mid-hip, -1 = skip the pair), n_pairs the same for every file; pairs 0 .. 8 are compute_height's
+        (include/p2s.h).  flags: per file, P2S_MEASURE_* of _lib.  close_to_zero_speed, head_factor: one value or one per
+        file.  n_speed_markers: per file, the summed speed runs over the table's first so many markers (None: all).  -> one dict per file:
+          sum_speeds [n_rows]; n_selected and angles [n_selected]: the mean angles of the speed-selected rows (NaN-filled
+          without P2S_MEASURE_ANGLES); kept_pos, kept_frame [n_kept]: the kept rows' places among the selected rows and
+          their frames, in the reference's order; all_slow, few_small_angles, all_data: the fallback branch that ran;
+          row_heights [n_kept]; height, leg_length; lengths [n_pairs]: the trimmed means; row_values [n_pairs + 2][n_kept]
+          when asked for (per-row lengths, heights, leg lengths)."""
+        fn = _entry(self._lib, 'p2s_body_measure_host')
+        tables = [np.ascontiguousarray(t, dtype=np.float64) for t in tables]
+        nf = len(tables)
+        if nf < 1 or any(t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 3 or t.shape[1] % 3 for t in tables):
+            raise P2sError('body_measure: at least one table, every table [n_rows >= 1][3 n_markers]')
+        n_rows = np.array([t.shape[0] for t in tables], dtype=np.int64)
+        n_mk = np.array([t.shape[1] // 3 for t in tables], dtype=np.int32)
+        roles = np.ascontiguousarray(marker_index, dtype=np.int32).reshape(nf, len(_lib.P2S_MEASURE_ROLES))
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(nf, -1, 2)
+        n_pairs = pairs.shape[1]
+        flags = np.ascontiguousarray(np.broadcast_to(np.asarray(flags, dtype=np.int32), (nf,)))
+        per_file = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (nf,)))   # noqa: E731
+        thr, head = per_file(close_to_zero_speed), per_file(head_factor)
+        n_speed = None if n_speed_markers is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_speed_markers, dtype=np.int32), (nf,)))
+        data = np.concatenate([t.reshape(-1) for t in tables])
+        N, ncol = int(n_rows.sum()), n_pairs + 2
+        speeds, angles, heights = np.empty(N), np.empty(N), np.empty(N)
+        pos, frame = np.empty(N, dtype=np.int32), np.empty(N, dtype=np.int32)
+        n_sel, n_kept, branch = (np.zeros(nf, dtype=np.int32) for _ in range(3))
+        values = np.empty((ncol, N)) if row_values else None
+        means = np.empty((nf, ncol))
+        _lib.check(fn(self._h, nf, _ptr(n_rows), _ptr(n_mk), _ptr(data), _ptr(flags), _ptr(roles), n_pairs, _optr(pairs), _ptr(head),
+                      _ptr(thr), _ptr(n_speed), 1 - float(fastest_frames_to_remove_percent), float(large_hip_knee_angles),
+                      float(trimmed_extrema_percent) / 2, _ptr(speeds), _ptr(angles), _ptr(n_sel), _ptr(pos), _ptr(frame),
+                      _ptr(n_kept), _ptr(branch), _ptr(heights), _ptr(values), _ptr(means)))
+        off = np.concatenate([[0], np.cumsum(n_rows)])
+        out = []
+        for f in range(nf):
+            o, k = off[f], int(n_kept[f])
+            res = {'sum_speeds': speeds[o:off[f + 1]], 'n_selected': int(n_sel[f]),
+                   'angles': angles[o:o + n_sel[f]],
+                   'kept_pos': pos[o:o + k].astype(np.int64), 'kept_frame': frame[o:o + k].astype(np.int64),
+                   'all_slow': bool(branch[f] & _lib.P2S_MEASURE_ALL_SLOW),
+                   'few_small_angles': bool(branch[f] & _lib.P2S_MEASURE_FEW_SMALL_ANGLES),
+                   'all_data': bool(branch[f] & _lib.P2S_MEASURE_ALL_DATA),
+                   'row_heights': heights[o:o + k], 'height': means[f, n_pairs], 'leg_length': means[f, n_pairs + 1],
+                   'lengths': means[f, :n_pairs]}
+            if row_values:
+                res['row_values'] = values[:, o:o + k]
+            out.append(res)
+        return out
+
+    def measure_kernel_ms(self):
+        """Kernel time of the last stable_argsort(), trimmed_means() or body_measure() call, from HIP events around its
+        kernels."""
+        fn = _entry(self._lib, 'p2s_measure_kernel_ms')
+        ms = C.c_float(0)
+        _lib.check(fn(self._h, C.byref(ms)))
+        return ms.value
+
     # -- np.mean / np.std of columns; 2D confidence statistics (Utilities/pose_confidence_analyze.py:118-219) ------------
     def column_mean_std(self, data):
         """data [n_rows][n_cols] float64 (any strides; NaN entries are skipped).  -> (mean [n_cols], std [n_cols], counts
