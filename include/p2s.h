@@ -382,6 +382,26 @@ int p2s_id_switch_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, co
 /* Milliseconds the kernels of this context's last p2s_id_switch_host took (HIP events around them). */
 int p2s_id_switch_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
 
+/* ---- primary-person selection (Utilities/pose_extract_person.py:37-87, the rule of p2s_json_select_tracked_person) ---------
+ * For every camera at once, as a prefix scan instead of a loop over the frames.  The layout is p2s_id_switch_host's: camera c
+ * has n_frames[c] >= 0 frames, the frames of all cameras stand back to back; persons [N][n_kpts][3] (x, y, confidence) holds
+ * the persons whose list has exactly 3 * n_kpts numbers, in list order (no other can be a candidate; a longer list ends the
+ * reference's run and is the caller's to deal with); person_off [frames + 1], person_off[0] = 0; 1 <= n_kpts <= 127.
+ * A person is a candidate when some keypoint has confidence > conf_threshold and a non-NaN x.  A frame with candidates
+ * selects one: the only one; else, after an earlier selection, the one with the strictly smallest mean distance to it over
+ * the keypoints valid in both (sqrt(dx*dx + dy*dy) without contraction, summed in np.mean's order, the first on ties; NaN,
+ * inf and no shared keypoint are not eligible); else the first candidate with the most confidences > conf_threshold.
+ * Per frame, camera-local indices, each output may be NULL:
+ *   chosen        the selected person as an index into the frame's run of `persons`, -1 for a frame without candidates
+ *   n_candidates  candidates of the frame
+ *   prev          the last earlier frame of the camera with a candidate, -1 without one
+ * More than 32 candidates in one frame: P2S_ERR_INVALID_ARG naming the camera and the frame, nothing computed.
+ * HOST pointers; blocks. */
+int p2s_track_select_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, const int64_t *person_off, const double *persons,
+                          int32_t n_kpts, double conf_threshold, int32_t *chosen, int32_t *n_candidates, int32_t *prev);
+/* Milliseconds the kernels of this context's last p2s_track_select_host took (HIP events around them). */
+int p2s_track_select_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
+
 /* ---- find_peaks (scipy.signal, 1.15.3) -----------------------------------------------------------------------------------
  * scipy.signal.find_peaks(x, prominence=p) for each of n_cols contiguous float64 columns of n_rows entries (column-major,
  * as p2s_column_order_stats_host takes them), bit for bit: _local_maxima_1d (a plateau's peak is (left_edge + right_edge)
@@ -671,6 +691,18 @@ int p2s_copy_files(const char *src_paths, const int64_t *src_offsets, const char
 #define P2S_TRACK_BAD_CONTENT (-3)
 int p2s_json_select_tracked_person(const p2s_json_batch *batch, int32_t n_kpts, double conf_threshold, double *out,
                                    int32_t *status, int32_t *detail);
+/* flags [total persons] (file-major, as p2s_json_person_lengths): what np.array() of the person's "pose_keypoints_2d" list
+ * would depend on beyond its numbers.  ALL_INTS: a non-empty list whose every element is a number token without fraction
+ * and exponent (Python reads ints, NumPy makes an int64 array); HAS_NULL / HAS_BOOL: it holds null / true or false;
+ * BIG_INT: an integer token beyond +-2^53, which float64 does not hold exactly; NOT_OBJECT: the person is not an object;
+ * BAD_LIST: the value of the key is not an array. */
+#define P2S_JSON_PERSON_ALL_INTS 1
+#define P2S_JSON_PERSON_HAS_NULL 2
+#define P2S_JSON_PERSON_HAS_BOOL 4
+#define P2S_JSON_PERSON_BIG_INT 8
+#define P2S_JSON_PERSON_NOT_OBJECT 16
+#define P2S_JSON_PERSON_BAD_LIST 32
+int p2s_json_person_flags(const p2s_json_batch *batch, int32_t *flags);
 
 /* ---- .trc data rows (host threads) ---------------------------------------------------------------------------
  * Replaces DataFrame.to_csv in make_trc (triangulation.py:214): appends n_rows lines
@@ -692,6 +724,16 @@ int p2s_format_float_repr(double value, char *out, int32_t capacity);
 int p2s_json_rewrite_people(const char *src_paths, const int64_t *src_offsets, const char *dst_paths,
                             const int64_t *dst_offsets, int64_t n_files, const int64_t *sel_offsets, const int32_t *sel,
                             int32_t n_threads, int8_t *written);
+
+/* ---- single-person JSON files (host threads) -----------------------------------------------------------------------
+ * The documents Utilities/pose_extract_person.py:process writes, byte for byte json.dump's text, for n_files paths at once
+ * (paths as in p2s_json_parse).  kind[i]: 0 = {"version": 1.3, "people": []}; 1 = one person, person_id [-1], its
+ * pose_keypoints_2d the 3 * n_kpts numbers values[i][...] as repr() floats (NaN, Infinity, -Infinity) and the seven other
+ * lists empty in the reference's key order; 2 = the same with the numbers as integers (values of kind 0 are not read).
+ * A value of kind 2 that is not an integer within int64, another kind, or 3 * n_kpts outside [1, 381]: P2S_ERR_INVALID_ARG
+ * before anything is written.  written [n_files] (may be NULL): 1 = file written, 0 = it could not be created or written. */
+int p2s_write_person_files(const char *paths, const int64_t *path_offsets, int64_t n_files, const double *values,
+                           const int8_t *kind, int32_t n_kpts, int32_t n_threads, int8_t *written);
 
 /* ---- proposals from the association result, first half (host threads) -----------------------------------------
  * The per-detection rows of person_index_per_cam (personAssociation.py:512-527) for every frame: rows[f][r][c] =

@@ -61,6 +61,7 @@ struct p2s_ctx {
     float id_switch_kernel_ms = -1.0f;               // p2s_id_switch_kernel_ms
     float gait_kernel_ms = -1.0f;                    // p2s_gait_kernel_ms
     float measure_kernel_ms = -1.0f;                 // p2s_measure_kernel_ms
+    float track_select_kernel_ms = -1.0f;            // p2s_track_select_kernel_ms
     hipStream_t side_stream = nullptr;               // search kernels run here, beside the next chunk's streaming pass
     hipEvent_t ev_k1[2] = {nullptr, nullptr}, ev_k2[2] = {nullptr, nullptr};
     Scratch slot[P2S_N_SLOTS];                       // staging of the *_host calls (Stage): no role, no owner between calls

@@ -36,6 +36,8 @@
 
 #include "p2s_ctx.h"
 #include "p2s_lsap.h"
+#include "p2s_npsum_small.h"
+#include "p2s_scan.h"
 
 #pragma clang fp contract(off)
 
@@ -80,42 +82,7 @@ constexpr int FLAG_TOO_MANY = 4;         // more than 32 kept persons in the fra
 
 __device__ __forceinline__ double ids_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
-struct OpMax {
-    static __device__ __forceinline__ int64_t identity() { return -1; }
-    static __device__ __forceinline__ int64_t apply(int64_t a, int64_t b) { return a > b ? a : b; }
-};
-struct OpSum {
-    static __device__ __forceinline__ int64_t identity() { return 0; }
-    static __device__ __forceinline__ int64_t apply(int64_t a, int64_t b) { return a + b; }
-};
-
-// Inclusive scan over the lanes of a wave.
-template <typename Op> __device__ __forceinline__ int64_t wave_scan(int64_t v, int lane) {
-    for (int s = 1; s < 64; s <<= 1) {
-        const int64_t up = __shfl_up(v, s);
-        if (lane >= s) v = Op::apply(v, up);
-    }
-    return v;
-}
-
-// Exclusive scan over the workgroup's lanes (whole waves, at most 16 of them); *total gets the value over all lanes.
-// `part` is LDS for one value a wave; called by every lane, two barriers.
-template <typename Op> __device__ int64_t block_scan_exclusive(int64_t mine, int64_t *part, int64_t *total) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = (int)(blockDim.x >> 6);
-    const int64_t incl = wave_scan<Op>(mine, lane);
-    int64_t before = __shfl_up(incl, 1);
-    if (lane == 0) before = Op::identity();
-    __syncthreads();                                              // part of an earlier call has been read
-    if (lane == 63) part[wave] = incl;
-    __syncthreads();
-    int64_t all = Op::identity();
-    for (int w = 0; w < n_waves; ++w) {
-        if (w < wave) before = Op::apply(part[w], before);
-        all = Op::apply(all, part[w]);
-    }
-    if (total) *total = all;
-    return before;
-}
+// OpMax, OpSum, wave_scan and block_scan_exclusive: p2s_scan.h
 
 // ---- the person filter ---------------------------------------------------------------------------------------------------
 // parse_frame_people :67-74: a person is dropped when every confidence is NaN or none is above 0 -- that is, kept when
@@ -201,23 +168,7 @@ __device__ __forceinline__ double match_cost(const double *pa, const double *pb,
         }
     }
     if (m < 3) return 1e9;                                        // MIN_VALID_KP
-    double sum;
-    if (m < 8) {
-        sum = 0.0;
-        for (int i = 0; i < m; ++i) sum = sum + d[i][lane];
-    } else {
-        double r[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = d[j][lane];
-        const int whole = m - m % 8;
-        for (int i = 8; i < whole; i += 8) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) r[j] = r[j] + d[i + j][lane];
-        }
-        sum = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (int i = whole; i < m; ++i) sum = sum + d[i][lane];
-    }
-    return sum / (double)m;
+    return p2s_np_sum_below_128<64>(&d[0][lane], m) / (double)m;
 }
 
 __global__ void __launch_bounds__(64) ids_match_kernel(const P2sIdsArgs a) {

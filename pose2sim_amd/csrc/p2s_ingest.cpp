@@ -27,6 +27,7 @@
 #include "p2s.h"
 #include "p2s_error.h"
 #include "p2s_host.h"
+#include "p2s_npsum_small.h"
 
 namespace {
 
@@ -40,7 +41,7 @@ enum PersonStatus : int8_t {
                           // synchronization gather: indexing that value raises in the reference)
 };
 
-enum : int8_t { kPersonNotObject = 1, kPersonHasNull = 2 };                    // Person::flags
+enum : int8_t { kPersonNotObject = 1, kPersonHasNull = 2, kPersonAllInts = 4, kPersonHasBool = 8, kPersonBigInt = 16 };   // Person::flags
 enum : int8_t { kFileTopObject = 1, kFilePeopleNull = 2, kFilePeopleOther = 4 };  // FileRec::flags; bits 3..5: kFileTopShift
 constexpr int kFileTopShift = 3;      // (P2S_JSON_DOC_LIST .. P2S_JSON_DOC_NULL) - P2S_JSON_DOC_LIST + 1 of a document that is no object
 
@@ -71,6 +72,7 @@ struct Parser {
     const char *p, *end;
     Arena *arena;
     bool ok = true;
+    bool number_is_int = false;   // the last number() had neither fraction nor exponent: Python reads an int
     // result for the current file
     bool have_people = false;
     size_t people_first = 0;
@@ -163,6 +165,7 @@ struct Parser {
                 p = q;
             }                                                               // else: "1e" -> number ends before 'e'
         }
+        number_is_int = p == int_end;
         if (!value) return true;
         double d = 0.0;
         const auto r = std::from_chars(s, p, d);
@@ -270,7 +273,8 @@ struct Parser {
         std::vector<double> &v = arena->values;
         person.off = (int64_t)v.size();
         person.status = kPersonOk;
-        person.flags &= (int8_t)~kPersonHasNull;
+        person.flags &= (int8_t)~(kPersonHasNull | kPersonAllInts | kPersonHasBool | kPersonBigInt);
+        bool all_ints = true;
         ws();
         if (p < end && *p == ']') {
             ++p;
@@ -283,8 +287,15 @@ struct Parser {
             if (p >= end) return fail();
             const char c = *p;
             double d;
+            number_is_int = false;                         // stays so for every literal
             if ((c >= '0' && c <= '9') || (c == '-' && !(p + 1 < end && p[1] == 'I'))) {
+                const char *token = p;
                 if (!number(&d)) return false;
+                if (number_is_int) {                       // an integer float64 does not hold exactly: beyond +-2^53
+                    long long exact = 0;
+                    const auto r = std::from_chars(token, p, exact);
+                    if (r.ec != std::errc() || exact > (1LL << 53) || exact < -(1LL << 53)) person.flags |= kPersonBigInt;
+                }
             } else if (c == 'N') {
                 if (!literal("NaN")) return false;
                 d = nan;
@@ -302,14 +313,18 @@ struct Parser {
             } else if (c == 't') {
                 if (!literal("true")) return false;
                 d = 1.0;
+                person.flags |= kPersonHasBool;
             } else if (c == 'f') {
                 if (!literal("false")) return false;
                 d = 0.0;
+                person.flags |= kPersonHasBool;
             } else {
                 if (!skip(4)) return false;                // string / array / object: not a number list
                 person.status = kPersonNonNumeric;
+                number_is_int = false;                     // whatever the skipped value held
                 d = nan;
             }
+            all_ints &= number_is_int;
             v.push_back(d);
             ws();
             if (p < end && *p == ',') {
@@ -323,6 +338,7 @@ struct Parser {
             return fail();
         }
         person.len = (int32_t)((int64_t)v.size() - person.off);
+        if (all_ints) person.flags |= kPersonAllInts;
         return true;
     }
     // One element of the "people" array.
@@ -579,6 +595,26 @@ int p2s_json_person_lengths(const p2s_json_batch *b, int32_t *lengths) {
     return P2S_OK;
 }
 
+int p2s_json_person_flags(const p2s_json_batch *b, int32_t *flags) {
+    if (!b || !flags) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
+    for (int64_t i = 0; i < b->n_files; ++i) {
+        const FileRec &fr = b->files[(size_t)i];
+        const Arena &arena = b->arenas[(size_t)fr.thread];
+        for (int32_t n = 0; n < fr.count; ++n) {
+            const Person &ps = arena.persons[(size_t)(fr.first_person + n)];
+            const bool list = ps.status == kPersonOk || ps.status == kPersonNonNumeric;
+            flags[b->person_base[(size_t)i] + n] =
+                (list && ps.len > 0 && (ps.flags & kPersonAllInts) ? P2S_JSON_PERSON_ALL_INTS : 0) |
+                (list && (ps.flags & kPersonHasNull) ? P2S_JSON_PERSON_HAS_NULL : 0) |
+                (list && (ps.flags & kPersonHasBool) ? P2S_JSON_PERSON_HAS_BOOL : 0) |
+                (list && (ps.flags & kPersonBigInt) ? P2S_JSON_PERSON_BIG_INT : 0) |
+                ((ps.flags & kPersonNotObject) ? P2S_JSON_PERSON_NOT_OBJECT : 0) |
+                (ps.status == kPersonBadList ? P2S_JSON_PERSON_BAD_LIST : 0);
+        }
+    }
+    return P2S_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -795,23 +831,8 @@ int p2s_json_person_ids(const p2s_json_batch *b, int64_t *text_off, char *text, 
     return P2S_OK;
 }
 
-// np.add.reduce over a contiguous float64 vector of fewer than 128 entries (NumPy's pairwise_sum): a plain loop below 8
-// entries, otherwise eight running sums over the whole blocks of eight, combined as a tree, then the tail one by one.
-static double numpy_sum_below_128(const double *a, int n) {
-    if (n < 8) {
-        double r = 0.0;
-        for (int i = 0; i < n; ++i) r += a[i];
-        return r;
-    }
-    double r[8];
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8)
-        for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += a[i];
-    return res;
-}
+// np.add.reduce over a contiguous float64 vector of fewer than 128 entries: the order of p2s_npsum_small.h
+static double numpy_sum_below_128(const double *a, int n) { return p2s_np_sum_below_128<1>(a, n); }
 
 int p2s_json_select_tracked_person(const p2s_json_batch *b, int32_t n_kpts, double conf_threshold, double *out,
                                    int32_t *status, int32_t *detail) {

@@ -411,3 +411,75 @@ int p2s_json_rewrite_people(const char *src_paths, const int64_t *src_offsets, c
 }
 
 }  // extern "C"
+
+// ---- single-person documents (Utilities/pose_extract_person.py:127-155) ---------------------------------------------
+namespace {
+
+const char kEmptyDocument[] = "{\"version\": 1.3, \"people\": []}";
+const char kPersonHead[] = "{\"version\": 1.3, \"people\": [{\"person_id\": [-1], \"pose_keypoints_2d\": [";
+const char kPersonTail[] = "], \"face_keypoints_2d\": [], \"hand_left_keypoints_2d\": [], \"hand_right_keypoints_2d\": [], "
+                           "\"pose_keypoints_3d\": [], \"face_keypoints_3d\": [], \"hand_left_keypoints_3d\": [], "
+                           "\"hand_right_keypoints_3d\": []}]}";
+
+// an integer a float64 holds that fits int64: [-2^63, 2^63)
+bool is_int64(double v) { return v == std::floor(v) && v >= -9223372036854775808.0 && v < 9223372036854775808.0; }
+
+}  // namespace
+
+extern "C" {
+
+int p2s_write_person_files(const char *paths, const int64_t *path_offsets, int64_t n_files, const double *values,
+                           const int8_t *kind, int32_t n_kpts, int32_t n_threads, int8_t *written) {
+    if (n_files < 0 || (n_files > 0 && (!paths || !path_offsets || !kind))) return p2s_set_error(P2S_ERR_INVALID_ARG, "bad arguments");
+    if (n_kpts < 1 || n_kpts > 127) return p2s_set_error(P2S_ERR_INVALID_ARG, "n_kpts=%d outside [1, 127]", n_kpts);
+    const int64_t nv = 3 * (int64_t)n_kpts;
+    for (int64_t i = 0; i < n_files; ++i) {
+        if (path_offsets[i + 1] < path_offsets[i]) return p2s_set_error(P2S_ERR_INVALID_ARG, "offsets must not decrease");
+        if (kind[i] < 0 || kind[i] > 2) return p2s_set_error(P2S_ERR_INVALID_ARG, "file %lld: kind %d outside [0, 2]", (long long)i, (int)kind[i]);
+        if (kind[i] != 0 && !values) return p2s_set_error(P2S_ERR_INVALID_ARG, "null values");
+        if (kind[i] == 2)
+            for (int64_t k = 0; k < nv; ++k)
+                if (!is_int64(values[i * nv + k]))
+                    return p2s_set_error(P2S_ERR_INVALID_ARG, "file %lld: value %lld is not an integer within int64", (long long)i, (long long)k);
+    }
+    const bool done = parallel_for(n_files, host_threads(n_threads, 64, n_files / 32 + 1), 32, [&](int, int64_t lo, int64_t hi) {
+        std::string out, dst;
+        char num[40];
+        for (int64_t i = lo; i < hi; ++i) {
+            dst.assign(paths + path_offsets[i], (size_t)(path_offsets[i + 1] - path_offsets[i]));
+            out.clear();
+            if (kind[i] == 0) {
+                out = kEmptyDocument;
+            } else {
+                out = kPersonHead;
+                for (int64_t k = 0; k < nv; ++k) {
+                    if (k) out += ", ";
+                    const double v = values[i * nv + k];
+                    if (kind[i] == 1) {
+                        Transcoder::put_float(out, v);
+                    } else {
+                        const auto r = std::to_chars(num, num + sizeof num, (long long)v);
+                        out.append(num, (size_t)(r.ptr - num));
+                    }
+                }
+                out += kPersonTail;
+            }
+            bool ok = false;
+            const int fd = open(dst.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+            if (fd >= 0) {
+                size_t at = 0;
+                ok = true;
+                while (at < out.size()) {
+                    const ssize_t w = write(fd, out.data() + at, out.size() - at);
+                    if (w <= 0) { ok = false; break; }
+                    at += (size_t)w;
+                }
+                if (close(fd) != 0) ok = false;
+            }
+            if (written) written[i] = ok ? 1 : 0;
+        }
+    });
+    return done ? P2S_OK : p2s_set_error(P2S_ERR_OOM, "out of host memory while writing");
+}
+
+}  // extern "C"

@@ -740,6 +740,45 @@ class Engine:
         _lib.check(fn(self._h, C.byref(ms)))
         return ms.value
 
+    # -- primary-person selection (Utilities/pose_extract_person.py:37-87) --------------------------------------------------
+    def track_select(self, cameras, n_kpts=26, conf_threshold=0.1):
+        """cameras: per camera (persons [N][n_kpts][3] float64, the persons whose list has exactly 3 * n_kpts numbers, of every
+        frame in list order; offsets [n_frames + 1], the first person of every frame), as for id_switch.  The reference's
+        _select_person along every camera, all cameras in one call and without a loop over the frames (csrc/p2s_extract.hip).
+        -> dict of per-camera int32 lists: 'chosen' the selected person as an index into the frame's own run (-1: the frame
+        has no candidate), 'n_candidates', 'prev' the last earlier frame with a candidate (-1: none).  More than 32
+        candidates in a frame are refused."""
+        fn = _entry(self._lib, 'p2s_track_select_host')
+        n_kpts = int(n_kpts)
+        persons, offsets = [], []
+        for p, o in cameras:
+            p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, max(n_kpts, 1), 3)
+            o = np.ascontiguousarray(o, dtype=np.int64).reshape(-1)
+            if len(o) < 1 or o[0] != 0 or o[-1] != len(p) or (np.diff(o) < 0).any():
+                raise P2sError('offsets must rise from 0 to the number of persons')
+            persons.append(p)
+            offsets.append(o)
+        Cn = len(persons)
+        if Cn < 1:
+            raise P2sError('at least one camera is required')
+        n_frames = np.array([len(o) - 1 for o in offsets], dtype=np.int64)
+        base = np.concatenate([[0], np.cumsum([len(p) for p in persons])])
+        off = np.concatenate([o[:-1] + b for o, b in zip(offsets, base[:-1])] + [base[-1:]]).astype(np.int64)
+        flat = persons[0] if Cn == 1 else np.concatenate(persons)
+        frames = int(n_frames.sum())
+        tables = np.zeros((3, frames), dtype=np.int32)
+        _lib.check(fn(self._h, Cn, _ptr(n_frames), _ptr(off), _optr(flat), n_kpts, float(conf_threshold), _optr(tables[0]),
+                      _optr(tables[1]), _optr(tables[2])))
+        f_off = np.concatenate([[0], np.cumsum(n_frames)])
+        return {name: [tables[i, f_off[c]:f_off[c + 1]] for c in range(Cn)] for i, name in enumerate(('chosen', 'n_candidates', 'prev'))}
+
+    def track_select_kernel_ms(self):
+        """Kernel time of the last track_select() call, from HIP events around its kernels."""
+        fn = _entry(self._lib, 'p2s_track_select_kernel_ms')
+        ms = C.c_float(0)
+        _lib.check(fn(self._h, C.byref(ms)))
+        return ms.value
+
     # -- synchronization (synchronization.py:1271-1343, 1541-1585) -------------------------------------------------------
     def sync_speeds(self, coords, b, a, zi):
         """coords: one [n_frames][n_cols] array per camera, the (x, y) columns of the keypoints to consider with the

@@ -64,6 +64,15 @@ class JsonBatch:
                 _lib.check(self._lib.p2s_json_person_lengths(self._h, _ptr(self._lengths)))
         return self._lengths
 
+    def person_flags(self):
+        """Per person (file-major): _lib.P2S_JSON_PERSON_* bits -- every number of the list an integer token, a null, a
+        boolean, an integer beyond +-2^53, the person not an object, the list not an array (p2s_json_person_flags)."""
+        fn = _entry(self._lib, 'p2s_json_person_flags')
+        flags = np.zeros(int(self.person_base[-1]), dtype=np.int32)
+        if flags.size:
+            _lib.check(fn(self._h, _ptr(flags)))
+        return flags
+
     def person_ids(self):
         """-> (ids, file_kind): ids, per person (file-major), the raw JSON text of its "person_id" value as bytes, None for
         a person without the key; file_kind [n_files] P2S_JSON_DOC_*: what `counts` does not tell apart about a file without
@@ -137,3 +146,20 @@ def copy_files(pairs, n_threads=0):
                             len(pairs), int(n_threads), None)
     if rc != 0:
         raise OSError(lib.p2s_last_error().decode())
+
+
+def write_person_files(paths, values, kind, n_kpts=26, n_threads=0):
+    """The single-person documents of Utilities/pose_extract_person.py, byte for byte json.dump's text, on host threads
+    (p2s_write_person_files): kind[i] 0 = no person, 1 = values[i] ([3 * n_kpts]) as repr() floats, 2 = as integers.
+    -> written [n_files] bool: False where the file could not be created or written."""
+    lib = _lib.load()
+    fn = _entry(lib, 'p2s_write_person_files')
+    enc = [p.encode() if not isinstance(p, bytes) else p for p in paths]
+    off = np.zeros(len(enc) + 1, dtype=np.int64)
+    if enc:
+        np.cumsum([len(e) for e in enc], out=off[1:])
+    values = np.ascontiguousarray(values, dtype=np.float64).reshape(len(enc), 3 * int(n_kpts))
+    kind = np.ascontiguousarray(kind, dtype=np.int8).reshape(len(enc))
+    written = np.zeros(len(enc), dtype=np.int8)
+    _lib.check(fn(b''.join(enc), off.ctypes.data_as(C.c_void_p), len(enc), _ptr(values), _ptr(kind), int(n_kpts), int(n_threads), _ptr(written)))
+    return written.astype(bool)
