@@ -288,73 +288,59 @@ int p2s_confidence_stats_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_fra
                               int32_t n_thresholds, const double *thresholds, double *stats, int64_t *counts, int64_t *below,
                               int64_t *bands) {
     if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
-    if (n_cams < 1 || n_cams > 65535) return p2s_set_error(P2S_ERR_INVALID_ARG, "n_cams=%d outside [1, 65535]", n_cams);
+    P2S_TRY(p2s_check_n_cams(n_cams));
     if (n_kpts < 1 || n_kpts > P2S_CONF_MAX_K) return p2s_set_error(P2S_ERR_INVALID_ARG, "n_kpts=%d outside [1, %d]", n_kpts, P2S_CONF_MAX_K);
     if (n_thresholds < 0 || n_thresholds > P2S_CONF_MAX_THRESHOLDS)
         return p2s_set_error(P2S_ERR_INVALID_ARG, "n_thresholds=%d outside [0, %d]", n_thresholds, P2S_CONF_MAX_THRESHOLDS);
     if (!n_frames || !tables || (n_thresholds > 0 && !thresholds)) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
     const size_t C = (size_t)n_cams, K = (size_t)n_kpts, nc = C * K, T = (size_t)n_thresholds;
-    // one block of 8-byte words, host and device: frame_off [C + 1], col_off [nc], col_len [nc], fractions [5],
-    // thresholds [8] go up; m [nc], below [8][nc], bands [nc][5], min and max [nc][2], mean and std [nc][2], order
-    // [nc][10], stats [nc][9] stay on the device
-    const size_t o_coff = C + 1, o_clen = o_coff + nc, o_frac = o_clen + nc, o_thr = o_frac + P2S_CONF_QUANTILES;
-    const size_t n_up = o_thr + P2S_CONF_MAX_THRESHOLDS;
-    const size_t o_m = n_up, o_below = o_m + nc, o_bands = o_below + P2S_CONF_MAX_THRESHOLDS * nc, o_mm = o_bands + P2S_CONF_BANDS * nc;
-    const size_t o_ms = o_mm + 2 * nc, o_ord = o_ms + 2 * nc, o_stats = o_ord + 2 * P2S_CONF_QUANTILES * nc;
-    const size_t n_words = o_stats + P2S_CONF_STATS * nc;
-    std::vector<int64_t> tab(n_up);
-    int64_t *frame_off = tab.data(), max_frames = 0;
-    frame_off[0] = 0;
-    for (size_t c = 0; c < C; ++c) {
-        if (n_frames[c] < 1 || n_frames[c] >= ((int64_t)1 << 31))
-            return p2s_set_error(P2S_ERR_INVALID_ARG, "camera %zu has %lld frames; expected 1 .. 2^31 - 1", c, (long long)n_frames[c]);
-        frame_off[c + 1] = frame_off[c] + n_frames[c];
-        max_frames = std::max(max_frames, n_frames[c]);
+    Layout lay;                                                   // `tab` goes up as one: what the host knows
+    const size_t o_foff = lay.add((C + 1) * 8), o_coff = lay.add(nc * 8), o_clen = lay.add(nc * 8), o_frac = lay.add(P2S_CONF_QUANTILES * 8),
+                 o_thr = lay.add(P2S_CONF_MAX_THRESHOLDS * 8), tab_b = lay.bytes;
+    // and what the kernels leave on the device
+    const size_t o_m = lay.add(nc * 8), o_below = lay.add(P2S_CONF_MAX_THRESHOLDS * nc * 8), o_bands = lay.add(P2S_CONF_BANDS * nc * 8), o_mm = lay.add(2 * nc * 8),
+                 o_ms = lay.add(2 * nc * 8), o_ord = lay.add(2 * P2S_CONF_QUANTILES * nc * 8), o_stats = lay.add(P2S_CONF_STATS * nc * 8);
+    std::vector<char> tab(tab_b);
+    int64_t *frame_off = (int64_t *)(tab.data() + o_foff), *col_off = (int64_t *)(tab.data() + o_coff), *col_len = (int64_t *)(tab.data() + o_clen);
+    P2sFrames fr;
+    P2S_TRY(fr.build(n_cams, n_frames, 1, (int64_t)1 << 33, frame_off));
+    const int64_t frames = fr.frames, max_frames = fr.max_frames;
+    for (size_t c = 0; c < C; ++c)
         for (size_t k = 0; k < K; ++k) {
-            tab[o_coff + c * K + k] = (int64_t)K * frame_off[c] + (int64_t)k * n_frames[c];
-            tab[o_clen + c * K + k] = n_frames[c];
+            col_off[c * K + k] = (int64_t)K * frame_off[c] + (int64_t)k * n_frames[c];
+            col_len[c * K + k] = n_frames[c];
         }
-    }
-    const int64_t frames = frame_off[C];
-    if (frames > ((int64_t)1 << 33)) return p2s_set_error(P2S_ERR_INVALID_ARG, "%lld frames are too many", (long long)frames);
-    double *up_f = (double *)tab.data();                          // the same 8-byte words, read as doubles on the device
+    double *up_frac = (double *)(tab.data() + o_frac), *up_thr = (double *)(tab.data() + o_thr);
     const double fractions[P2S_CONF_QUANTILES] = {5 / 100.0, 25 / 100.0, 50 / 100.0, 75 / 100.0, 95 / 100.0};   // np.percentile: q / 100
-    for (int i = 0; i < P2S_CONF_QUANTILES; ++i) up_f[o_frac + i] = fractions[i];
-    for (size_t t = 0; t < P2S_CONF_MAX_THRESHOLDS; ++t) up_f[o_thr + t] = t < T ? thresholds[t] : 0.0;
+    for (int i = 0; i < P2S_CONF_QUANTILES; ++i) up_frac[i] = fractions[i];
+    for (size_t t = 0; t < P2S_CONF_MAX_THRESHOLDS; ++t) up_thr[t] = t < T ? thresholds[t] : 0.0;
     const size_t table_b = (size_t)frames * K * sizeof(double);
     HIP_TRY(hipSetDevice(ctx->device));
     P2sConfArgs a{};
     Stage st{ctx};
-    int64_t *sm;
+    char *sm;
     P2S_TRY(st.upload(a.tables, tables, table_b));
     P2S_TRY(st.alloc(a.cols, table_b));
     P2S_TRY(st.alloc(a.valid, table_b));
-    P2S_TRY(st.alloc(sm, n_words * 8));
-    P2S_TRY(st.up(sm, tab.data(), n_up * 8));
-    a.frame_off = sm; a.col_off = sm + o_coff; a.col_len = sm + o_clen;
+    P2S_TRY(st.alloc(sm, lay.bytes));
+    P2S_TRY(st.up(sm, tab.data(), tab_b));
+    a.frame_off = (const int64_t *)(sm + o_foff); a.col_off = (const int64_t *)(sm + o_coff); a.col_len = (const int64_t *)(sm + o_clen);
     a.fractions = (const double *)(sm + o_frac); a.thresholds = (const double *)(sm + o_thr);
-    a.m = sm + o_m; a.below = sm + o_below; a.bands = sm + o_bands;
+    a.m = (int64_t *)(sm + o_m); a.below = (int64_t *)(sm + o_below); a.bands = (int64_t *)(sm + o_bands);
     a.minmax = (double *)(sm + o_mm); a.mean_std = (double *)(sm + o_ms);
     a.order = (const double *)(sm + o_ord); a.stats = (double *)(sm + o_stats);
     a.max_frames = max_frames;
     a.C = n_cams; a.K = n_kpts; a.n_cols = (int32_t)nc; a.n_thr = n_thresholds;
-    HIP_TRY(hipEventRecord(ctx->ev_stage[0], ctx->stream));
+    P2S_TRY(st.time_begin());
     HIP_TRY(launch_confidence(a, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_stage[1], ctx->stream));
+    P2S_TRY(st.time_end());
     P2S_TRY(st.down(stats, a.stats, P2S_CONF_STATS * nc * 8));
     P2S_TRY(st.down(counts, a.m, nc * 8));
     P2S_TRY(st.down(below, a.below, T * nc * 8));
     P2S_TRY(st.down(bands, a.bands, P2S_CONF_BANDS * nc * 8));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));                   // `tab` is host memory: alive until here
-    HIP_TRY(hipEventElapsedTime(&ctx->confidence_kernel_ms, ctx->ev_stage[0], ctx->ev_stage[1]));
-    return P2S_OK;
+    return st.finish(P2S_TIMED_CONFIDENCE);                       // `tab` is host memory: alive until here
 }
 
-int p2s_confidence_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) {
-    if (!ctx || !elapsed_ms) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
-    if (ctx->confidence_kernel_ms < 0.0f) return p2s_set_error(P2S_ERR_INVALID_ARG, "p2s_confidence_stats_host has not run on this context");
-    *elapsed_ms = ctx->confidence_kernel_ms;
-    return P2S_OK;
-}
+int p2s_confidence_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) { return p2s_kernel_ms_query(ctx, P2S_TIMED_CONFIDENCE, "p2s_confidence_stats_host", elapsed_ms); }
 
 }  // extern "C"

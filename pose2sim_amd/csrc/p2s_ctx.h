@@ -1,10 +1,13 @@
 // p2s_ctx.h -- the per-GPU context behind include/p2s.h's opaque p2s_ctx, and what the C-ABI entry points (p2s_api.hip
-// and the tail of every stage's kernel file) share to use it: HIP_TRY / P2S_TRY, the grow-only Scratch buffer, and
-// Stage, which hands a *_host call its device buffers.
+// and the tail of every stage's kernel file) share to use it: HIP_TRY / P2S_TRY, the grow-only Scratch buffer, Stage,
+// which hands a *_host call its device buffers and times its kernels (one slot of p2s_ctx::kernel_ms a stage, read
+// back by p2s_kernel_ms_query), Layout, which carves one block into arrays, and the checked frame and person offsets
+// of the per-camera analysis stages (P2sFrames).
 #ifndef P2S_CTX_H
 #define P2S_CTX_H
 
 #include <hip/hip_runtime.h>
+#include <string.h>
 
 #include "p2s.h"
 #include "p2s_error.h"
@@ -44,6 +47,10 @@ struct Scratch {
 
 #define P2S_N_SLOTS 8
 
+// The stages that time their own kernels: one slot of p2s_ctx::kernel_ms each.
+enum { P2S_TIMED_REPROJ, P2S_TIMED_JITTER, P2S_TIMED_CONFIDENCE, P2S_TIMED_ID_SWITCH, P2S_TIMED_GAIT, P2S_TIMED_MEASURE,
+       P2S_TIMED_TRACK_SELECT, P2S_N_TIMED };
+
 struct p2s_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -55,13 +62,7 @@ struct p2s_ctx {
     bool full_calib = false;     // K, dist, R, T, newK were provided
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_stage[2] = {nullptr, nullptr};     // around the kernels of the *_host call that times itself
-    float reproj_kernel_ms = -1.0f;                  // p2s_reproject_kernel_ms: the last call's kernel time
-    float jitter_kernel_ms = -1.0f;                  // p2s_jitter_kernel_ms
-    float confidence_kernel_ms = -1.0f;              // p2s_confidence_kernel_ms
-    float id_switch_kernel_ms = -1.0f;               // p2s_id_switch_kernel_ms
-    float gait_kernel_ms = -1.0f;                    // p2s_gait_kernel_ms
-    float measure_kernel_ms = -1.0f;                 // p2s_measure_kernel_ms
-    float track_select_kernel_ms = -1.0f;            // p2s_track_select_kernel_ms
+    float kernel_ms[P2S_N_TIMED] = {-1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f};   // the last call's kernel time of every P2S_TIMED_* stage; -1: has not run
     hipStream_t side_stream = nullptr;               // search kernels run here, beside the next chunk's streaming pass
     hipEvent_t ev_k1[2] = {nullptr, nullptr}, ev_k2[2] = {nullptr, nullptr};
     Scratch slot[P2S_N_SLOTS];                       // staging of the *_host calls (Stage): no role, no owner between calls
@@ -107,6 +108,76 @@ struct Stage {
     }
     int down(void *h, const void *d, size_t bytes) const {
         if (h && bytes) HIP_TRY(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return P2S_OK;
+    }
+    // A call that times itself: time_begin, its launches, time_end, its downloads, finish(P2S_TIMED_*).
+    int time_begin() const {
+        HIP_TRY(hipEventRecord(ctx->ev_stage[0], ctx->stream));
+        return P2S_OK;
+    }
+    int time_end() const {
+        HIP_TRY(hipEventRecord(ctx->ev_stage[1], ctx->stream));
+        return P2S_OK;
+    }
+    int finish(int which) const {                                     // the stream's work is done when this returns
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(hipEventElapsedTime(&ctx->kernel_ms[which], ctx->ev_stage[0], ctx->ev_stage[1]));
+        return P2S_OK;
+    }
+};
+
+// The body of every p2s_*_kernel_ms.  `who` names what has to run first: one entry point ("<who> has not run on this
+// context"), or a phrase over several that carries its own negation ("neither a nor b", "none of a, b and c": "<who>
+// has run on this context").
+inline int p2s_kernel_ms_query(p2s_ctx *ctx, int which, const char *who, float *out) {
+    if (!ctx || !out) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
+    if (ctx->kernel_ms[which] < 0.0f)
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "%s has %srun on this context", who, strchr(who, ' ') ? "" : "not ");
+    *out = ctx->kernel_ms[which];
+    return P2S_OK;
+}
+
+// One block of arrays, each at a multiple of 16 bytes: add() hands out the offsets in bytes, a host block and a device
+// block carved by the same calls match, and what is added first is a prefix that goes up as one copy.
+struct Layout {
+    size_t bytes = 0;
+    size_t add(size_t n) {
+        const size_t at = bytes;
+        bytes += (n + 15) / 16 * 16;
+        return at;
+    }
+};
+
+// The cameras of a per-camera analysis call (jitter, confidence, id_switch, track_select), frames back to back.
+inline int p2s_check_n_cams(int32_t n_cams) {
+    if (n_cams < 1 || n_cams > 65535) return p2s_set_error(P2S_ERR_INVALID_ARG, "n_cams=%d outside [1, 65535]", n_cams);
+    return P2S_OK;
+}
+
+struct P2sFrames {
+    int64_t frames = 0, max_frames = 0;
+    // frame_off [n_cams + 1] from the cameras' frame counts, each min_frames (0 or 1) .. 2^31 - 1 and at most max_total
+    // together.  frame_off is the caller's storage: it goes up, so it has to live until the stream is synchronized.
+    int build(int32_t n_cams, const int64_t *n_frames, int min_frames, int64_t max_total, int64_t *frame_off) {
+        frame_off[0] = 0;
+        for (size_t c = 0; c < (size_t)n_cams; ++c) {
+            if (n_frames[c] < min_frames || n_frames[c] >= ((int64_t)1 << 31))
+                return p2s_set_error(P2S_ERR_INVALID_ARG, "camera %zu has %lld frames; expected %d .. 2^31 - 1", c, (long long)n_frames[c], min_frames);
+            frame_off[c + 1] = frame_off[c] + n_frames[c];
+            if (n_frames[c] > max_frames) max_frames = n_frames[c];
+        }
+        frames = frame_off[n_cams];
+        if (frames > max_total) return p2s_set_error(P2S_ERR_INVALID_ARG, "%lld frames are too many", (long long)frames);
+        return P2S_OK;
+    }
+    // person_off [frames + 1], the first person of every one of these frames, and the persons it indexes: their number.
+    int persons(const int64_t *person_off, const void *persons, int64_t &N) const {
+        if (person_off[0] != 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "person_off must start at 0");
+        for (int64_t f = 0; f < frames; ++f)
+            if (person_off[f + 1] < person_off[f]) return p2s_set_error(P2S_ERR_INVALID_ARG, "person_off must not decrease (frame %lld)", (long long)f);
+        N = person_off[frames];
+        if (N >= ((int64_t)1 << 31)) return p2s_set_error(P2S_ERR_INVALID_ARG, "%lld persons are too many", (long long)N);
+        if (N > 0 && !persons) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
         return P2S_OK;
     }
 };

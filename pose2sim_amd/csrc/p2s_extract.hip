@@ -10,8 +10,8 @@
 //   ext_person_kernel      per person: the number of confidences above the threshold and the candidate flag
 //   ext_frame_kernel       per frame: its candidates in list order, their count, the fallback choice (the first candidate
 //                          with the most confidences); per tile of 256 frames the last frame with a candidate
-//   ext_tile_scan_kernel   per camera: running maximum over those tiles
-//   ext_prev_kernel        per frame: the last earlier frame with a candidate
+//   cam_tile_scan_kernel   (p2s_scan.h) per camera: running maximum over those tiles
+//   cam_prev_kernel        (p2s_scan.h) per frame: the last earlier frame with a candidate
 //   ext_map_kernel         per frame, one wave: map[f][j] for every candidate j of the previous selecting frame.  A frame
 //                          without candidates gets the identity, a frame with one candidate and the first selecting frame
 //                          of a camera a constant map
@@ -56,7 +56,7 @@ struct P2sExtArgs {
 
 namespace {
 
-constexpr int TILE = 256;                // frames per workgroup of the per-frame passes
+constexpr int TILE = CAM_TILE;           // frames per workgroup of the per-frame passes: the shared scan's tile, 256
 constexpr int T = 32;                    // frames per tile of the map scan: one lane of a 32-lane group each
 constexpr int GROUPS = 8;                // tiles per workgroup of the two walks
 constexpr int MC = P2S_EXT_MAX_CAND;
@@ -103,36 +103,6 @@ __global__ void __launch_bounds__(TILE) ext_frame_kernel(const P2sExtArgs a) {
     int64_t last;
     (void)block_scan_exclusive<OpMax>(key, part, &last);
     if (tid == 0) a.tile_value[(int64_t)c * a.ptiles + blockIdx.x] = last;
-}
-
-__global__ void __launch_bounds__(1024) ext_tile_scan_kernel(const P2sExtArgs a) {
-    __shared__ int64_t part[16];
-    const int c = blockIdx.x, tid = threadIdx.x;
-    const int64_t F = a.frame_off[c + 1] - a.frame_off[c];
-    const int64_t nt = (F + TILE - 1) / TILE;                     // <= a.ptiles
-    const int64_t *in = a.tile_value + (int64_t)c * a.ptiles;
-    int64_t *out = a.tile_before + (int64_t)c * a.ptiles;
-    int64_t carry = OpMax::identity();
-    for (int64_t base = 0; base < nt; base += 1024) {             // uniform trip count
-        const int64_t i = base + tid;
-        int64_t total;
-        const int64_t before = block_scan_exclusive<OpMax>(i < nt ? in[i] : OpMax::identity(), part, &total);
-        if (i < nt) out[i] = OpMax::apply(carry, before);
-        carry = OpMax::apply(carry, total);
-    }
-}
-
-__global__ void __launch_bounds__(TILE) ext_prev_kernel(const P2sExtArgs a) {
-    __shared__ int64_t part[TILE / 64];
-    const int c = blockIdx.y, tid = threadIdx.x;
-    const int64_t f_base = a.frame_off[c], F = a.frame_off[c + 1] - f_base;
-    const int64_t t0 = (int64_t)blockIdx.x * TILE;
-    if (t0 >= F) return;
-    const int64_t f = t0 + tid;
-    const int64_t key = f < F && a.count[f_base + f] > 0 ? f : -1;
-    int64_t before = block_scan_exclusive<OpMax>(key, part, nullptr);
-    before = OpMax::apply(before, a.tile_before[(int64_t)c * a.ptiles + blockIdx.x]);
-    if (f < F) a.prev[f_base + f] = (int32_t)before;
 }
 
 // ---- the transition map of a frame ---------------------------------------------------------------------------------------
@@ -274,9 +244,10 @@ hipError_t launch_track_select(const P2sExtArgs &a, int64_t max_frames, hipStrea
     const dim3 ptiles((unsigned)a.ptiles, (unsigned)a.C);
     const dim3 wtiles((unsigned)((a.tiles + GROUPS - 1) / GROUPS), (unsigned)a.C);
     if (a.N > 0) hipLaunchKernelGGL(ext_person_kernel, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, s, a);
+    const CamScanArgs sc{a.frame_off, a.count, a.tile_value, a.tile_before, a.prev, nullptr, nullptr, a.C, a.ptiles};
     hipLaunchKernelGGL(ext_frame_kernel, ptiles, dim3(TILE), 0, s, a);
-    hipLaunchKernelGGL(ext_tile_scan_kernel, dim3((unsigned)a.C), dim3(1024), 0, s, a);
-    hipLaunchKernelGGL(ext_prev_kernel, ptiles, dim3(TILE), 0, s, a);
+    hipLaunchKernelGGL(cam_tile_scan_kernel<OpMax>, dim3((unsigned)a.C), dim3(1024), 0, s, sc);
+    hipLaunchKernelGGL(cam_prev_kernel, ptiles, dim3(TILE), 0, s, sc);
     hipLaunchKernelGGL(ext_map_kernel, dim3((unsigned)max_frames, (unsigned)a.C), dim3(64), ((size_t)a.K + 1) * 64 * sizeof(double), s, a);   // at most 64 KiB
     hipLaunchKernelGGL(ext_tile_agg_kernel, wtiles, dim3(GROUPS * 32), 0, s, a);
     hipLaunchKernelGGL(ext_agg_scan_kernel, dim3((unsigned)a.C), dim3(1024), 0, s, a);
@@ -292,27 +263,16 @@ extern "C" {
 int p2s_track_select_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, const int64_t *person_off, const double *persons,
                           int32_t n_kpts, double conf_threshold, int32_t *chosen, int32_t *n_candidates, int32_t *prev) {
     if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
-    if (n_cams < 1 || n_cams > 65535) return p2s_set_error(P2S_ERR_INVALID_ARG, "n_cams=%d outside [1, 65535]", n_cams);
+    P2S_TRY(p2s_check_n_cams(n_cams));
     if (n_kpts < 1 || n_kpts > P2S_EXT_MAX_KPTS) return p2s_set_error(P2S_ERR_INVALID_ARG, "n_kpts=%d outside [1, %d]", n_kpts, P2S_EXT_MAX_KPTS);
     if (!n_frames || !person_off) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
     const size_t C = (size_t)n_cams;
     std::vector<int64_t> frame_off(C + 1);
-    int64_t max_frames = 0;
-    frame_off[0] = 0;
-    for (size_t c = 0; c < C; ++c) {
-        if (n_frames[c] < 0 || n_frames[c] >= ((int64_t)1 << 31))
-            return p2s_set_error(P2S_ERR_INVALID_ARG, "camera %zu has %lld frames; expected 0 .. 2^31 - 1", c, (long long)n_frames[c]);
-        frame_off[c + 1] = frame_off[c] + n_frames[c];
-        max_frames = std::max(max_frames, n_frames[c]);
-    }
-    const int64_t frames = frame_off[C];
-    if (frames >= ((int64_t)1 << 31)) return p2s_set_error(P2S_ERR_INVALID_ARG, "%lld frames are too many", (long long)frames);
-    if (person_off[0] != 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "person_off must start at 0");
-    for (int64_t f = 0; f < frames; ++f)
-        if (person_off[f + 1] < person_off[f]) return p2s_set_error(P2S_ERR_INVALID_ARG, "person_off must not decrease (frame %lld)", (long long)f);
-    const int64_t N = person_off[frames];
-    if (N >= ((int64_t)1 << 31)) return p2s_set_error(P2S_ERR_INVALID_ARG, "%lld persons are too many", (long long)N);
-    if (N > 0 && !persons) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
+    P2sFrames fr;
+    int64_t N;
+    P2S_TRY(fr.build(n_cams, n_frames, 0, ((int64_t)1 << 31) - 1, frame_off.data()));
+    P2S_TRY(fr.persons(person_off, persons, N));
+    const int64_t frames = fr.frames, max_frames = fr.max_frames;
     // more than 32 candidates need more than 32 listed persons: only such a frame is counted here
     const int64_t values = 3 * (int64_t)n_kpts;
     for (size_t c = 0; c < C; ++c)
@@ -330,42 +290,36 @@ int p2s_track_select_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames,
                                      (long long)(f - frame_off[c]), (long long)n, P2S_EXT_MAX_CAND);
         }
     const int64_t ptiles = std::max<int64_t>((max_frames + TILE - 1) / TILE, 1), tiles = std::max<int64_t>((max_frames + T - 1) / T, 1);
-    // 8-byte words: frame_off [C + 1], person_off [frames + 1], tile_value, tile_before [C][ptiles]
-    const size_t o_poff = C + 1, o_tv = o_poff + (size_t)frames + 1, o_tb = o_tv + C * (size_t)ptiles, n_words = o_tb + C * (size_t)ptiles;
-    // bytes: map [frames][32], agg [C][tiles][32], entry [C][tiles], fallback [frames]
-    const size_t o_agg = (size_t)frames * MC, o_entry = o_agg + C * (size_t)tiles * MC, o_fb = o_entry + C * (size_t)tiles, n_bytes = o_fb + (size_t)frames;
+    Layout lw, lb;                                                // 8-byte words; bytes
+    const size_t n_ptile = C * (size_t)ptiles, n_tile = C * (size_t)tiles;
+    const size_t o_foff = lw.add((C + 1) * 8), o_poff = lw.add(((size_t)frames + 1) * 8), o_tv = lw.add(n_ptile * 8), o_tb = lw.add(n_ptile * 8);
+    const size_t o_map = lb.add((size_t)frames * MC), o_agg = lb.add(n_tile * MC), o_entry = lb.add(n_tile), o_fb = lb.add((size_t)frames);
     HIP_TRY(hipSetDevice(ctx->device));
     P2sExtArgs a{};
     Stage st{ctx};
-    int64_t *words;
+    char *words;
     int32_t *ints;
     uint8_t *bytes;
     P2S_TRY(st.upload(a.persons, persons, (size_t)N * values * sizeof(double)));
-    P2S_TRY(st.alloc(words, n_words * 8));
-    P2S_TRY(st.up(words, frame_off.data(), (C + 1) * 8));
+    P2S_TRY(st.alloc(words, lw.bytes));
+    P2S_TRY(st.up(words + o_foff, frame_off.data(), (C + 1) * 8));
     P2S_TRY(st.up(words + o_poff, person_off, ((size_t)frames + 1) * 8));
     P2S_TRY(st.alloc(ints, (2 * (size_t)N + 3 * (size_t)frames) * sizeof(int32_t)));
-    P2S_TRY(st.alloc(bytes, n_bytes));
-    a.frame_off = words; a.person_off = words + o_poff; a.tile_value = words + o_tv; a.tile_before = words + o_tb;
+    P2S_TRY(st.alloc(bytes, lb.bytes));
+    a.frame_off = (const int64_t *)(words + o_foff); a.person_off = (const int64_t *)(words + o_poff);
+    a.tile_value = (int64_t *)(words + o_tv); a.tile_before = (int64_t *)(words + o_tb);
     a.count = ints; a.prev = ints + frames; a.chosen = ints + 2 * frames; a.pinfo = ints + 3 * frames; a.cand_list = a.pinfo + N;
-    a.map = bytes; a.agg = bytes + o_agg; a.entry = bytes + o_entry; a.fallback = bytes + o_fb;
+    a.map = bytes + o_map; a.agg = bytes + o_agg; a.entry = bytes + o_entry; a.fallback = bytes + o_fb;
     a.thr = conf_threshold; a.N = N; a.C = n_cams; a.K = n_kpts; a.ptiles = (int32_t)ptiles; a.tiles = (int32_t)tiles;
-    HIP_TRY(hipEventRecord(ctx->ev_stage[0], ctx->stream));
+    P2S_TRY(st.time_begin());
     HIP_TRY(launch_track_select(a, max_frames, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_stage[1], ctx->stream));
+    P2S_TRY(st.time_end());
     P2S_TRY(st.down(n_candidates, a.count, (size_t)frames * sizeof(int32_t)));
     P2S_TRY(st.down(prev, a.prev, (size_t)frames * sizeof(int32_t)));
     P2S_TRY(st.down(chosen, a.chosen, (size_t)frames * sizeof(int32_t)));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));                   // frame_off and person_off are host memory: alive until here
-    HIP_TRY(hipEventElapsedTime(&ctx->track_select_kernel_ms, ctx->ev_stage[0], ctx->ev_stage[1]));
-    return P2S_OK;
+    return st.finish(P2S_TIMED_TRACK_SELECT);                     // frame_off and person_off are host memory: alive until here
 }
 
-int p2s_track_select_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) {
-    if (!ctx || !elapsed_ms) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
-    if (ctx->track_select_kernel_ms < 0.0f) return p2s_set_error(P2S_ERR_INVALID_ARG, "p2s_track_select_host has not run on this context");
-    *elapsed_ms = ctx->track_select_kernel_ms;
-    return P2S_OK;
-}
+int p2s_track_select_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) { return p2s_kernel_ms_query(ctx, P2S_TIMED_TRACK_SELECT, "p2s_track_select_host", elapsed_ms); }
 
 }  // extern "C"

@@ -457,19 +457,18 @@ int p2s_find_peaks_host(p2s_ctx *ctx, int64_t n_rows, int32_t n_cols, const doub
     a.capacity = capacity;
     const int64_t tiles = std::max<int64_t>(a.n_blocks, (a.max_cand + FB - 1) / FB);
     const size_t mc = (size_t)a.max_cand, cap = (size_t)capacity;
-    // small block: tile_off [tiles] i64, n_cand, n_kept i64, bounds [n_cols] f64, tile_count [tiles] u32, col_count [n_cols] i32
-    const size_t o_mp = ((size_t)tiles + 2) * 8, o_tc = o_mp + (size_t)n_cols * 8, o_cc = o_tc + (size_t)tiles * 4;
-    const size_t small_b = o_cc + (size_t)n_cols * 4;
+    Layout lay;                                                   // tile_off, then n_cand and n_kept right behind it
+    const size_t o_toff = lay.add(((size_t)tiles + 2) * 8), o_mp = lay.add((size_t)n_cols * 8), o_tc = lay.add((size_t)tiles * 4), o_cc = lay.add((size_t)n_cols * 4);
     HIP_TRY(hipSetDevice(ctx->device));
     Stage st{ctx};
     char *sm, *cd, *ob;
     P2S_TRY(st.upload(a.x, data, (size_t)a.total * sizeof(double)));
     P2S_TRY(st.alloc(a.sum, (size_t)a.n_blocks * sizeof(FpSummary)));
     P2S_TRY(st.alloc(a.mark, (size_t)a.total));
-    P2S_TRY(st.alloc(sm, small_b));
+    P2S_TRY(st.alloc(sm, lay.bytes));
     P2S_TRY(st.alloc(cd, mc * 25 + 16));                          // cand i64, prom f64, lb, rb i32, keep u8
     P2S_TRY(st.alloc(ob, cap * 32 + 16));                         // peak, lb, rb i64, prom f64
-    a.tile_off = (long long *)sm;
+    a.tile_off = (long long *)(sm + o_toff);
     a.n_cand = a.tile_off + tiles; a.n_kept = a.n_cand + 1;
     a.tile_count = (uint32_t *)(sm + o_tc);
     if (prominence) {
@@ -485,14 +484,13 @@ int p2s_find_peaks_host(p2s_ctx *ctx, int64_t n_rows, int32_t n_cols, const doub
     a.out_prom = (double *)(a.out_rb + cap);
     HIP_TRY(hipMemsetAsync(a.mark, 0, (size_t)a.total, ctx->stream));
     HIP_TRY(hipMemsetAsync(a.col_count, 0, (size_t)n_cols * 4, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_stage[0], ctx->stream));
+    P2S_TRY(st.time_begin());
     HIP_TRY(p2s_launch_find_peaks(a, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_stage[1], ctx->stream));
+    P2S_TRY(st.time_end());
     long long found = 0;
     P2S_TRY(st.down(&found, a.n_kept, 8));
     P2S_TRY(st.down(col_counts, a.col_count, (size_t)n_cols * 4));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));                   // `found` is host memory: alive until here
-    HIP_TRY(hipEventElapsedTime(&ctx->gait_kernel_ms, ctx->ev_stage[0], ctx->ev_stage[1]));
+    P2S_TRY(st.finish(P2S_TIMED_GAIT));                           // `found` is host memory: alive until here
     const size_t n_copy = (size_t)std::min<int64_t>(found, capacity);
     if (n_copy > 0) {
         P2S_TRY(st.down(peaks, a.out_peak, n_copy * 8));
@@ -541,14 +539,15 @@ int p2s_gait_contacts_host(p2s_ctx *ctx, int32_t method, int32_t n_cols, int64_t
     }
     const size_t nc = (size_t)n_cols, cells = (size_t)(max_rows - 1) * nc, cap = (size_t)event_capacity;
     const size_t work_rows = (size_t)(max_rows - 1) + (method == P2S_GAIT_HEIGHT ? 2 * (size_t)g.padlen : 0);
-    // small block: col_len [nc] i64, dt, threshold, factor [nc] f64, weights, n_on, n_off [nc] i32, first_low [nc] u8
     const size_t nw = method == P2S_GAIT_VELOCITY ? (size_t)n_weights : 0;
-    const size_t o_w = nc * 32, o_non = o_w + nw * 8, o_first = o_non + nc * 8, small_b = o_first + nc;
-    std::vector<char> host_small(o_non);
-    memcpy(host_small.data(), col_len, nc * 8);
-    memcpy(host_small.data() + nc * 8, dt, nc * 8);
-    memcpy(host_small.data() + nc * 16, threshold, nc * 8);
-    memcpy(host_small.data() + nc * 24, factor, nc * 8);
+    Layout lay;                                                   // `host_small` goes up as one: what the caller gave
+    const size_t o_len = lay.add(nc * 8), o_dt = lay.add(nc * 8), o_thr = lay.add(nc * 8), o_fac = lay.add(nc * 8), o_w = lay.add(nw * 8), up_b = lay.bytes;
+    const size_t o_non = lay.add(nc * 4), o_noff = lay.add(nc * 4), o_first = lay.add(nc);   // and what the kernels count
+    std::vector<char> host_small(up_b);
+    memcpy(host_small.data() + o_len, col_len, nc * 8);
+    memcpy(host_small.data() + o_dt, dt, nc * 8);
+    memcpy(host_small.data() + o_thr, threshold, nc * 8);
+    memcpy(host_small.data() + o_fac, factor, nc * 8);
     if (nw) memcpy(host_small.data() + o_w, weights, nw * 8);
     HIP_TRY(hipSetDevice(ctx->device));
     Stage st{ctx};
@@ -556,34 +555,29 @@ int p2s_gait_contacts_host(p2s_ctx *ctx, int32_t method, int32_t n_cols, int64_t
     P2S_TRY(st.upload(g.in, data, (size_t)max_rows * nc * sizeof(double)));
     P2S_TRY(st.alloc(g.sig, cells * sizeof(double)));
     P2S_TRY(st.alloc(g.work, work_rows * nc * sizeof(double)));
-    P2S_TRY(st.alloc(sm, small_b));
+    P2S_TRY(st.alloc(sm, lay.bytes));
     P2S_TRY(st.alloc(g.on, 2 * nc * cap * 4 + 16));
-    P2S_TRY(st.up(sm, host_small.data(), o_non));
+    P2S_TRY(st.up(sm, host_small.data(), up_b));
     g.off = g.on + nc * cap;
-    g.col_len = (const int64_t *)sm;
-    g.dt = (const double *)(sm + nc * 8); g.threshold = g.dt + nc; g.factor = g.threshold + nc;
+    g.col_len = (const int64_t *)(sm + o_len);
+    g.dt = (const double *)(sm + o_dt); g.threshold = (const double *)(sm + o_thr); g.factor = (const double *)(sm + o_fac);
     g.w = (const double *)(sm + o_w);
-    g.n_on = (int32_t *)(sm + o_non); g.n_off = g.n_on + nc;
+    g.n_on = (int32_t *)(sm + o_non); g.n_off = (int32_t *)(sm + o_noff);
     g.first_low = (uint8_t *)(sm + o_first);
-    HIP_TRY(hipEventRecord(ctx->ev_stage[0], ctx->stream));
+    P2S_TRY(st.time_begin());
     HIP_TRY(p2s_launch_gait(g, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_stage[1], ctx->stream));
+    P2S_TRY(st.time_end());
     P2S_TRY(st.down(signal, g.sig, cells * sizeof(double)));
     P2S_TRY(st.down(n_on, g.n_on, nc * 4));
     P2S_TRY(st.down(n_off, g.n_off, nc * 4));
     P2S_TRY(st.down(first_low, g.first_low, nc));
     P2S_TRY(st.down(on, g.on, nc * cap * 4));
     P2S_TRY(st.down(off, g.off, nc * cap * 4));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));                   // `host_small` is host memory: alive until here
-    HIP_TRY(hipEventElapsedTime(&ctx->gait_kernel_ms, ctx->ev_stage[0], ctx->ev_stage[1]));
-    return P2S_OK;
+    return st.finish(P2S_TIMED_GAIT);                             // `host_small` is host memory: alive until here
 }
 
 int p2s_gait_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) {
-    if (!ctx || !elapsed_ms) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
-    if (ctx->gait_kernel_ms < 0.0f) return p2s_set_error(P2S_ERR_INVALID_ARG, "neither p2s_find_peaks_host nor p2s_gait_contacts_host has run on this context");
-    *elapsed_ms = ctx->gait_kernel_ms;
-    return P2S_OK;
+    return p2s_kernel_ms_query(ctx, P2S_TIMED_GAIT, "neither p2s_find_peaks_host nor p2s_gait_contacts_host", elapsed_ms);
 }
 
 }  // extern "C"

@@ -3,10 +3,10 @@
 //
 //   ids_filter_kernel      per frame: the persons parse_frame_people keeps (some confidence above 0), their count and their
 //                          stable list; per tile of 256 frames the last frame that holds a person
-//   ids_tile_scan_kernel   per camera: exclusive scan of the tiles' values -- a running maximum (the last frame with a
-//                          person before the tile) or a running sum (the matched distances before the tile)
-//   ids_prev_kernel        per frame: the last earlier frame with a person (analyze_camera's prev_people) and the number of
-//                          empty frames since (its zero_count)
+//   cam_tile_scan_kernel   (p2s_scan.h) per camera: exclusive scan of the tiles' values -- a running maximum (the last frame
+//                          with a person before the tile) or a running sum (the matched distances before the tile)
+//   cam_prev_kernel        (p2s_scan.h) per frame: the last earlier frame with a person (analyze_camera's prev_people) and
+//                          the number of empty frames since (its zero_count)
 //   ids_match_kernel       per frame with persons and a previous frame: the cost matrix (compute_match_cost), scipy's
 //                          linear_sum_assignment (p2s_lsap.h), the matched distances in previous-person order, the numbers
 //                          of unmatched previous and current persons
@@ -30,6 +30,7 @@
 // integers and every sum of them is a scan: no atomic of any kind, two runs give the same bytes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <vector>
@@ -52,7 +53,7 @@ struct P2sIdsArgs {
     const int64_t *frame_off;    // [C + 1]
     int32_t *valid_list;         // [N] from person_off[f]: the kept persons of frame f, as indices into the frame's list
     int32_t *count, *prev, *zero_run, *n_matched, *n_lost, *n_appeared, *flag;   // [frames] each
-    int64_t *tile_value;         // [C][tiles] what ids_tile_scan_kernel scans
+    int64_t *tile_value;         // [C][tiles] what cam_tile_scan_kernel scans
     int64_t *tile_before;        // [C][tiles] its result
     int64_t *n_dist;             // [C] the running sum's total: matched distances of the camera
     double *stage;               // [N] from person_off[f]: the matched distances of frame f
@@ -77,7 +78,7 @@ struct P2sLsapArgs {
 
 namespace {
 
-constexpr int TILE = 256;                // frames per workgroup of the per-frame passes
+constexpr int TILE = CAM_TILE;           // frames per workgroup of the per-frame passes: the shared scan's tile, 256
 constexpr int FLAG_TOO_MANY = 4;         // more than 32 kept persons in the frame or in its previous one: not matched
 
 __device__ __forceinline__ double ids_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
@@ -112,43 +113,8 @@ __global__ void __launch_bounds__(TILE) ids_filter_kernel(const P2sIdsArgs a) {
     if (tid == 0) a.tile_value[(int64_t)c * a.tiles + blockIdx.x] = last;
 }
 
-// ---- scan of the tiles of a camera ---------------------------------------------------------------------------------------
-template <typename Op> __global__ void __launch_bounds__(1024) ids_tile_scan_kernel(const P2sIdsArgs a) {
-    __shared__ int64_t part[16];
-    const int c = blockIdx.x, tid = threadIdx.x;
-    const int64_t F = a.frame_off[c + 1] - a.frame_off[c];
-    const int64_t nt = (F + TILE - 1) / TILE;                     // <= a.tiles
-    const int64_t *in = a.tile_value + (int64_t)c * a.tiles;
-    int64_t *out = a.tile_before + (int64_t)c * a.tiles;
-    int64_t carry = Op::identity();
-    for (int64_t base = 0; base < nt; base += 1024) {             // uniform trip count
-        const int64_t i = base + tid;
-        int64_t total;
-        const int64_t before = block_scan_exclusive<Op>(i < nt ? in[i] : Op::identity(), part, &total);
-        if (i < nt) out[i] = Op::apply(carry, before);
-        carry = Op::apply(carry, total);
-    }
-    if (tid == 0 && a.n_dist) a.n_dist[c] = carry;
-}
-
-// ---- the previous frame ---------------------------------------------------------------------------------------------------
-// prev[f] = the last frame before f of the same camera with a kept person, -1 without one; zero_run[f] = the frames
-// between the two, f - 1 - prev[f]: analyze_camera's zero_count when it reaches frame f.
-__global__ void __launch_bounds__(TILE) ids_prev_kernel(const P2sIdsArgs a) {
-    __shared__ int64_t part[TILE / 64];
-    const int c = blockIdx.y, tid = threadIdx.x;
-    const int64_t f_base = a.frame_off[c], F = a.frame_off[c + 1] - f_base;
-    const int64_t t0 = (int64_t)blockIdx.x * TILE;
-    if (t0 >= F) return;
-    const int64_t f = t0 + tid;
-    const int64_t key = f < F && a.count[f_base + f] > 0 ? f : -1;
-    int64_t before = block_scan_exclusive<OpMax>(key, part, nullptr);
-    before = OpMax::apply(before, a.tile_before[(int64_t)c * a.tiles + blockIdx.x]);
-    if (f < F) {
-        a.prev[f_base + f] = (int32_t)before;
-        a.zero_run[f_base + f] = (int32_t)(f - 1 - before);
-    }
-}
+// The scan of the tiles of a camera and the previous frame of every frame -- prev[f], and zero_run[f]: analyze_camera's
+// zero_count when it reaches frame f -- are cam_tile_scan_kernel and cam_prev_kernel of p2s_scan.h.
 
 // ---- cost matrix and assignment -------------------------------------------------------------------------------------------
 struct MatchShared {
@@ -276,16 +242,16 @@ hipError_t launch_id_switch(const P2sIdsArgs &a, hipStream_t s) {
     const dim3 tiles((unsigned)a.tiles, (unsigned)a.C);
     const int64_t cells = (int64_t)a.C * a.n_rows;
     hipLaunchKernelGGL(ids_fill_nan_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, a.table, cells);
+    CamScanArgs sc{a.frame_off, a.count, a.tile_value, a.tile_before, a.prev, a.zero_run, nullptr, a.C, a.tiles};
     if (a.max_frames > 0) {
-        P2sIdsArgs first = a;
-        first.n_dist = nullptr;                                   // the running maximum has no total to keep
         hipLaunchKernelGGL(ids_filter_kernel, tiles, dim3(TILE), 0, s, a);
-        hipLaunchKernelGGL(ids_tile_scan_kernel<OpMax>, dim3((unsigned)a.C), dim3(1024), 0, s, first);
-        hipLaunchKernelGGL(ids_prev_kernel, tiles, dim3(TILE), 0, s, a);
+        hipLaunchKernelGGL(cam_tile_scan_kernel<OpMax>, dim3((unsigned)a.C), dim3(1024), 0, s, sc);   // the running maximum has no total to keep
+        hipLaunchKernelGGL(cam_prev_kernel, tiles, dim3(TILE), 0, s, sc);
         hipLaunchKernelGGL(ids_match_kernel, dim3((unsigned)a.max_frames, (unsigned)a.C), dim3(64), 0, s, a);
         hipLaunchKernelGGL(ids_count_kernel, tiles, dim3(TILE), 0, s, a);
     }
-    hipLaunchKernelGGL(ids_tile_scan_kernel<OpSum>, dim3((unsigned)a.C), dim3(1024), 0, s, a);   // no frame at all: n_dist = 0
+    sc.totals = a.n_dist;
+    hipLaunchKernelGGL(cam_tile_scan_kernel<OpSum>, dim3((unsigned)a.C), dim3(1024), 0, s, sc);   // no frame at all: n_dist = 0
     if (a.max_frames > 0) hipLaunchKernelGGL(ids_gather_kernel, tiles, dim3(TILE), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -334,63 +300,49 @@ extern "C" {
 int p2s_id_switch_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, const int64_t *person_off, const double *persons,
                        int32_t *tables, int32_t *kept, double *distances, int64_t *n_distances, double *stats) {
     if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
-    if (n_cams < 1 || n_cams > 65535) return p2s_set_error(P2S_ERR_INVALID_ARG, "n_cams=%d outside [1, 65535]", n_cams);
+    P2S_TRY(p2s_check_n_cams(n_cams));
     if (!n_frames || !person_off) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
     const size_t C = (size_t)n_cams;
-    // 8-byte words that go up: frame_off [C + 1], fractions [3], person_off [frames + 1]
-    std::vector<int64_t> head(C + 1 + P2S_IDS_QUANTILES);
-    int64_t max_frames = 0;
-    head[0] = 0;
-    for (size_t c = 0; c < C; ++c) {
-        if (n_frames[c] < 0 || n_frames[c] >= ((int64_t)1 << 31))
-            return p2s_set_error(P2S_ERR_INVALID_ARG, "camera %zu has %lld frames; expected 0 .. 2^31 - 1", c, (long long)n_frames[c]);
-        head[c + 1] = head[c] + n_frames[c];
-        max_frames = std::max(max_frames, n_frames[c]);
-    }
-    const int64_t frames = head[C];
-    if (frames >= ((int64_t)1 << 31)) return p2s_set_error(P2S_ERR_INVALID_ARG, "%lld frames are too many", (long long)frames);
-    if (person_off[0] != 0) return p2s_set_error(P2S_ERR_INVALID_ARG, "person_off must start at 0");
+    Layout lay;                                                   // `head` goes up as one: frame_off, np.percentile's fractions
+    const size_t o_foff = lay.add((C + 1) * 8), o_frac = lay.add(P2S_IDS_QUANTILES * 8), head_b = lay.bytes;
+    std::vector<char> head(head_b);
+    int64_t *frame_off = (int64_t *)(head.data() + o_foff), N;
+    P2sFrames fr;
+    P2S_TRY(fr.build(n_cams, n_frames, 0, ((int64_t)1 << 31) - 1, frame_off));
+    P2S_TRY(fr.persons(person_off, persons, N));
+    const int64_t frames = fr.frames, max_frames = fr.max_frames;
     int64_t n_rows = 1;                                           // the longest camera's persons: room for its distances
-    for (size_t c = 0; c < C; ++c) {
-        for (int64_t f = head[c]; f < head[c + 1]; ++f)
-            if (person_off[f + 1] < person_off[f]) return p2s_set_error(P2S_ERR_INVALID_ARG, "person_off must not decrease (frame %lld)", (long long)f);
-        n_rows = std::max(n_rows, person_off[head[c + 1]] - person_off[head[c]]);
-    }
-    const int64_t N = person_off[frames];
-    if (N >= ((int64_t)1 << 31)) return p2s_set_error(P2S_ERR_INVALID_ARG, "%lld persons are too many", (long long)N);
-    if (N > 0 && !persons) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
+    for (size_t c = 0; c < C; ++c) n_rows = std::max(n_rows, person_off[frame_off[c + 1]] - person_off[frame_off[c]]);
     const double fractions[P2S_IDS_QUANTILES] = {50 / 100.0, 95 / 100.0, 99 / 100.0};   // np.percentile: q / 100
-    for (int i = 0; i < P2S_IDS_QUANTILES; ++i) ((double *)head.data())[C + 1 + i] = fractions[i];
+    memcpy(head.data() + o_frac, fractions, sizeof fractions);
     const int64_t tiles = std::max<int64_t>((max_frames + TILE - 1) / TILE, 1);
-    const size_t n_head = head.size(), n_poff = (size_t)frames + 1, n_tile = C * (size_t)tiles;
-    // and words that stay on the device: tile_value, tile_before [C][tiles], n_dist, m [C], min and max, mean and std
-    // [C][2], order [C][6], stats [C][6]
-    const size_t o_poff = n_head, o_tv = o_poff + n_poff, o_tb = o_tv + n_tile, o_nd = o_tb + n_tile, o_m = o_nd + C, o_mm = o_m + C;
-    const size_t o_ms = o_mm + 2 * C, o_ord = o_ms + 2 * C, o_stats = o_ord + 2 * P2S_IDS_QUANTILES * C, n_words = o_stats + P2S_IDS_STATS * C;
+    const size_t n_poff = (size_t)frames + 1, n_tile = C * (size_t)tiles;
+    const size_t o_poff = lay.add(n_poff * 8), o_tv = lay.add(n_tile * 8), o_tb = lay.add(n_tile * 8), o_nd = lay.add(C * 8), o_m = lay.add(C * 8),
+                 o_mm = lay.add(2 * C * 8), o_ms = lay.add(2 * C * 8), o_ord = lay.add(2 * P2S_IDS_QUANTILES * C * 8), o_stats = lay.add(P2S_IDS_STATS * C * 8);
     const size_t cells = C * (size_t)n_rows;
     HIP_TRY(hipSetDevice(ctx->device));
     P2sIdsArgs a{};
     Stage st{ctx};
-    int64_t *sm;
+    char *sm;
     int32_t *ints;
     P2S_TRY(st.upload(a.persons, persons, (size_t)N * P2S_IDS_VALUES * sizeof(double)));
-    P2S_TRY(st.alloc(sm, n_words * 8));
-    P2S_TRY(st.up(sm, head.data(), n_head * 8));
+    P2S_TRY(st.alloc(sm, lay.bytes));
+    P2S_TRY(st.up(sm, head.data(), head_b));
     P2S_TRY(st.up(sm + o_poff, person_off, n_poff * 8));
     P2S_TRY(st.alloc(ints, ((size_t)P2S_IDS_TABLES * frames + N) * sizeof(int32_t)));
     P2S_TRY(st.alloc(a.stage, (size_t)N * sizeof(double)));
     P2S_TRY(st.alloc(a.table, cells * sizeof(double)));
     P2S_TRY(st.alloc(a.valid, cells * sizeof(double)));
-    a.frame_off = sm; a.fractions = (const double *)(sm + C + 1); a.person_off = sm + o_poff;
-    a.tile_value = sm + o_tv; a.tile_before = sm + o_tb; a.n_dist = sm + o_nd; a.m = sm + o_m;
+    a.frame_off = (const int64_t *)(sm + o_foff); a.fractions = (const double *)(sm + o_frac); a.person_off = (const int64_t *)(sm + o_poff);
+    a.tile_value = (int64_t *)(sm + o_tv); a.tile_before = (int64_t *)(sm + o_tb); a.n_dist = (int64_t *)(sm + o_nd); a.m = (int64_t *)(sm + o_m);
     a.minmax = (double *)(sm + o_mm); a.mean_std = (double *)(sm + o_ms); a.order = (double *)(sm + o_ord); a.stats = (double *)(sm + o_stats);
     a.count = ints; a.prev = ints + frames; a.zero_run = ints + 2 * frames; a.n_matched = ints + 3 * frames;
     a.n_lost = ints + 4 * frames; a.n_appeared = ints + 5 * frames; a.flag = ints + 6 * frames;
     a.valid_list = ints + (size_t)P2S_IDS_TABLES * frames;
     a.n_rows = n_rows; a.max_frames = max_frames; a.C = n_cams; a.tiles = (int32_t)tiles;
-    HIP_TRY(hipEventRecord(ctx->ev_stage[0], ctx->stream));
+    P2S_TRY(st.time_begin());
     HIP_TRY(launch_id_switch(a, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_stage[1], ctx->stream));
+    P2S_TRY(st.time_end());
     std::vector<int64_t> nd(C);
     std::vector<double> table(distances ? cells : 0);
     P2S_TRY(st.down(tables, ints, (size_t)P2S_IDS_TABLES * frames * sizeof(int32_t)));
@@ -398,8 +350,7 @@ int p2s_id_switch_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, co
     P2S_TRY(st.down(nd.data(), a.n_dist, C * 8));
     P2S_TRY(st.down(stats, a.stats, P2S_IDS_STATS * C * 8));
     if (distances) P2S_TRY(st.down(table.data(), a.table, cells * sizeof(double)));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));                   // `head` and person_off are host memory: alive until here
-    HIP_TRY(hipEventElapsedTime(&ctx->id_switch_kernel_ms, ctx->ev_stage[0], ctx->ev_stage[1]));
+    P2S_TRY(st.finish(P2S_TIMED_ID_SWITCH));                      // `head` and person_off are host memory: alive until here
     int64_t at = 0;                                               // the cameras' distances back to back
     for (size_t c = 0; c < C; ++c) {
         if (n_distances) n_distances[c] = nd[c];
@@ -445,11 +396,6 @@ int p2s_lsap_host(p2s_ctx *ctx, int64_t n, int32_t n_rows, int32_t n_cols, const
     return P2S_OK;
 }
 
-int p2s_id_switch_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) {
-    if (!ctx || !elapsed_ms) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
-    if (ctx->id_switch_kernel_ms < 0.0f) return p2s_set_error(P2S_ERR_INVALID_ARG, "p2s_id_switch_host has not run on this context");
-    *elapsed_ms = ctx->id_switch_kernel_ms;
-    return P2S_OK;
-}
+int p2s_id_switch_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) { return p2s_kernel_ms_query(ctx, P2S_TIMED_ID_SWITCH, "p2s_id_switch_host", elapsed_ms); }
 
 }  // extern "C"

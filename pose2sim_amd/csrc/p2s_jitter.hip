@@ -484,51 +484,47 @@ int p2s_jitter_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, const
                     double *thresholds, double *median_area, uint8_t *mask, int32_t *counts, int64_t event_capacity,
                     int32_t *events, int64_t *n_events) {
     if (!ctx) return p2s_set_error(P2S_ERR_INVALID_ARG, "null context");
-    if (n_cams < 1 || n_cams > 65535) return p2s_set_error(P2S_ERR_INVALID_ARG, "n_cams=%d outside [1, 65535]", n_cams);
+    P2S_TRY(p2s_check_n_cams(n_cams));
     if (!n_frames || !series) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
     if (event_capacity < 0 || (event_capacity > 0 && !events)) return p2s_set_error(P2S_ERR_INVALID_ARG, "event_capacity=%lld without room", (long long)event_capacity);
     constexpr int K = P2S_JITTER_KPTS, NS = K + 1;
     const size_t C = (size_t)n_cams;
-    // host tables: frame_off [C+1], tile_base [C+1], col_off [C*27], col_len [C*27]
-    std::vector<int64_t> tab(2 * (C + 1) + 2 * C * NS);
-    int64_t *frame_off = tab.data(), *tile_base = frame_off + C + 1, *col_off = tile_base + C + 1, *col_len = col_off + C * NS;
-    int64_t max_frames = 0;
-    frame_off[0] = tile_base[0] = 0;
-    for (size_t c = 0; c < C; ++c) {
-        if (n_frames[c] < 1 || n_frames[c] >= ((int64_t)1 << 31))
-            return p2s_set_error(P2S_ERR_INVALID_ARG, "camera %zu has %lld frames; expected 1 .. 2^31 - 1", c, (long long)n_frames[c]);
-        frame_off[c + 1] = frame_off[c] + n_frames[c];
-        tile_base[c + 1] = tile_base[c] + (n_frames[c] - 1 + 255) / 256;
-        max_frames = std::max(max_frames, n_frames[c]);
-    }
-    const int64_t frames = frame_off[C], rows = frames - n_cams, n_tiles = tile_base[C];
-    if (frames > ((int64_t)1 << 33)) return p2s_set_error(P2S_ERR_INVALID_ARG, "%lld frames are too many", (long long)frames);
+    Layout lay;                                                   // `tab` goes up as one: the host's tables
+    const size_t o_foff = lay.add((C + 1) * 8), o_tbase = lay.add((C + 1) * 8), o_coff = lay.add(C * NS * 8), o_clen = lay.add(C * NS * 8), tab_b = lay.bytes;
+    std::vector<char> tab(tab_b);
+    int64_t *frame_off = (int64_t *)(tab.data() + o_foff), *tile_base = (int64_t *)(tab.data() + o_tbase);
+    int64_t *col_off = (int64_t *)(tab.data() + o_coff), *col_len = (int64_t *)(tab.data() + o_clen);
+    P2sFrames fr;
+    P2S_TRY(fr.build(n_cams, n_frames, 1, (int64_t)1 << 33, frame_off));
+    const int64_t frames = fr.frames, max_frames = fr.max_frames, rows = frames - n_cams;
+    tile_base[0] = 0;
     for (size_t c = 0; c < C; ++c) {                              // displacement columns, then the areas, in one allocation
         const int64_t R = n_frames[c] - 1;
+        tile_base[c + 1] = tile_base[c] + (R + 255) / 256;
         for (int k = 0; k < K; ++k) { col_off[c * NS + k] = K * (frame_off[c] - (int64_t)c) + k * R; col_len[c * NS + k] = R; }
         col_off[c * NS + K] = K * rows + frame_off[c];
         col_len[c * NS + K] = n_frames[c];
     }
+    const int64_t n_tiles = tile_base[C];
     const size_t series_b = (size_t)frames * K * 3 * sizeof(double), disp_b = (size_t)rows * K * sizeof(double);
-    const size_t area_b = (size_t)frames * sizeof(double), tab_b = tab.size() * sizeof(int64_t);
-    // small device block after the tables: stats [C*27][2] f64, stat counts [C*27] i64, medians, thresholds [C*26] f64,
-    // median area [C] f64, n_events i64, counts [C*26] i32
-    const size_t o_stats = tab_b, o_scnt = o_stats + C * NS * 16, o_med = o_scnt + C * NS * 8, o_thr = o_med + C * K * 8;
-    const size_t o_marea = o_thr + C * K * 8, o_nev = o_marea + C * 8, o_cnt = o_nev + 8, small_b = o_cnt + C * K * 4;
+    const size_t area_b = (size_t)frames * sizeof(double);
+    // and what stays on the device: the columns' two middle values and non-NaN counts, what the kernels derive from them
+    const size_t o_stats = lay.add(C * NS * 16), o_scnt = lay.add(C * NS * 8), o_med = lay.add(C * K * 8), o_thr = lay.add(C * K * 8),
+                 o_marea = lay.add(C * 8), o_nev = lay.add(8), o_cnt = lay.add(C * K * 4);
     HIP_TRY(hipSetDevice(ctx->device));
     P2sJitterArgs a{};
     Stage st{ctx};
     char *sm;
     P2S_TRY(st.upload(a.series, series, series_b));
     P2S_TRY(st.alloc(a.disp, disp_b + area_b));
-    P2S_TRY(st.alloc(sm, small_b));
+    P2S_TRY(st.alloc(sm, lay.bytes));
     P2S_TRY(st.alloc(a.tile_off, (size_t)n_tiles * 16 + 16));
     P2S_TRY(st.alloc(a.mask, (size_t)rows * K + 16));
     P2S_TRY(st.alloc(a.edge, (size_t)frames));
     P2S_TRY(st.alloc(a.events, (size_t)event_capacity * 16 + 16));
     P2S_TRY(st.up(sm, tab.data(), tab_b));
-    a.frame_off = (const int64_t *)sm;
-    a.tile_base = a.frame_off + C + 1;
+    a.frame_off = (const int64_t *)(sm + o_foff);
+    a.tile_base = (const int64_t *)(sm + o_tbase);
     a.area = a.disp + (size_t)rows * K;
     a.stats = (const double *)(sm + o_stats);
     a.stat_counts = (const int64_t *)(sm + o_scnt);
@@ -544,15 +540,15 @@ int p2s_jitter_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, const
     a.C = n_cams;
     P2sOrderArgs o{};
     o.data = a.disp;
-    o.col_off = a.tile_base + C + 1;
-    o.col_len = o.col_off + C * NS;
+    o.col_off = (const int64_t *)(sm + o_coff);
+    o.col_len = (const int64_t *)(sm + o_clen);
     o.out = (double *)(sm + o_stats);
     o.counts = (int64_t *)(sm + o_scnt);
     o.n_cols = n_cams * NS; o.n_ranks = 2;                        // ranks NULL: the two middle positions
     HIP_TRY(hipMemsetAsync(a.counts, 0, C * K * 4, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_stage[0], ctx->stream));
+    P2S_TRY(st.time_begin());
     HIP_TRY(p2s_launch_jitter(a, o, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_stage[1], ctx->stream));
+    P2S_TRY(st.time_end());
     long long found = 0;
     P2S_TRY(st.down(&found, a.n_events, 8));
     P2S_TRY(st.down(displacements, a.disp, disp_b));
@@ -562,8 +558,7 @@ int p2s_jitter_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, const
     P2S_TRY(st.down(median_area, a.med_area, C * 8));
     P2S_TRY(st.down(mask, a.mask, (size_t)rows * K));
     P2S_TRY(st.down(counts, a.counts, C * K * 4));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));                   // `tab` and `found` are host memory: alive until here
-    HIP_TRY(hipEventElapsedTime(&ctx->jitter_kernel_ms, ctx->ev_stage[0], ctx->ev_stage[1]));
+    P2S_TRY(st.finish(P2S_TIMED_JITTER));                         // `tab` and `found` are host memory: alive until here
     const int64_t n_copy = std::min<int64_t>(found, event_capacity);
     if (n_copy > 0) {
         P2S_TRY(st.down(events, a.events, (size_t)n_copy * 16));
@@ -573,11 +568,6 @@ int p2s_jitter_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames, const
     return P2S_OK;
 }
 
-int p2s_jitter_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) {
-    if (!ctx || !elapsed_ms) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
-    if (ctx->jitter_kernel_ms < 0.0f) return p2s_set_error(P2S_ERR_INVALID_ARG, "p2s_jitter_host has not run on this context");
-    *elapsed_ms = ctx->jitter_kernel_ms;
-    return P2S_OK;
-}
+int p2s_jitter_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) { return p2s_kernel_ms_query(ctx, P2S_TIMED_JITTER, "p2s_jitter_host", elapsed_ms); }
 
 }  // extern "C"

@@ -438,16 +438,6 @@ static hipError_t p2s_launch_sort(const MsSort &s, int64_t n_tiles, int n_cols, 
     return hipGetLastError();
 }
 
-// A host block of arrays, each at a multiple of 16 bytes, uploaded as one; the same offsets carve a device block.
-struct MsLayout {
-    size_t bytes = 0;
-    size_t add(size_t n) {
-        const size_t at = bytes;
-        bytes += (n + 15) / 16 * 16;
-        return at;
-    }
-};
-
 // Segment offsets and the tile table for segments of `len` records (each 1 .. 2^31 - 1, checked by the caller).
 static void ms_tiles(int64_t n_seg, const int64_t *len, std::vector<int64_t> &row_off, std::vector<int32_t> &tile_seg, std::vector<int32_t> &tile_idx, int64_t &total, int64_t &longest) {
     row_off.resize((size_t)n_seg);
@@ -486,14 +476,14 @@ struct MsColumns {
         len32.resize((size_t)n_seg);
         for (int64_t i = 0; i < n_seg; ++i) len32[(size_t)i] = (int32_t)seg_len[i];
         const size_t ns = (size_t)n_seg, nt = tile_seg.size(), n = (size_t)total;
-        MsLayout sm;
+        Layout sm;
         const size_t o_off = sm.add(ns * 8), o_len = sm.add(ns * 4), o_ts = sm.add(nt * 4), o_ti = sm.add(nt * 4);
         std::vector<char> host(sm.bytes);
         memcpy(host.data() + o_off, row_off.data(), ns * 8);
         memcpy(host.data() + o_len, len32.data(), ns * 4);
         memcpy(host.data() + o_ts, tile_seg.data(), nt * 4);
         memcpy(host.data() + o_ti, tile_idx.data(), nt * 4);
-        MsLayout rc;
+        Layout rc;
         const size_t o_k0 = rc.add(n * 8), o_k1 = rc.add(n * 8), o_i0 = rc.add(n * 4), o_i1 = rc.add(n * 4), o_ord = rc.add(n * 4), o_sorted = rc.add(want_sorted ? n * 8 : 0);
         P2S_TRY(st.upload(s.src, data, n * sizeof(double)));
         P2S_TRY(st.upload(small, host.data(), sm.bytes));
@@ -508,7 +498,7 @@ struct MsColumns {
         s.idx[0] = (uint32_t *)(rec + o_i0); s.idx[1] = (uint32_t *)(rec + o_i1);
         s.order = (int32_t *)(rec + o_ord);
         s.sorted = want_sorted ? (double *)(rec + o_sorted) : nullptr;
-        HIP_TRY(hipEventRecord(ctx->ev_stage[0], ctx->stream));
+        P2S_TRY(st.time_begin());
         HIP_TRY(p2s_launch_sort(s, (int64_t)nt, 1, longest, ctx->stream));
         return P2S_OK;
     }
@@ -525,11 +515,9 @@ int p2s_stable_argsort_host(p2s_ctx *ctx, int64_t n_segments, const int64_t *seg
     Stage st{ctx};
     MsColumns c;
     P2S_TRY(c.run(ctx, st, n_segments, seg_len, data, false));
-    HIP_TRY(hipEventRecord(ctx->ev_stage[1], ctx->stream));
+    P2S_TRY(st.time_end());
     P2S_TRY(st.down(order, c.s.order, (size_t)c.total * 4));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipEventElapsedTime(&ctx->measure_kernel_ms, ctx->ev_stage[0], ctx->ev_stage[1]));
-    return P2S_OK;
+    return st.finish(P2S_TIMED_MEASURE);
 }
 
 int p2s_trimmed_means_host(p2s_ctx *ctx, int64_t n_segments, const int64_t *seg_len, const double *data, double half_trim, double *means) {
@@ -548,11 +536,9 @@ int p2s_trimmed_means_host(p2s_ctx *ctx, int64_t n_segments, const int64_t *seg_
     t.means = d_means; t.col_stride = 0; t.half_trim = half_trim;
     hipLaunchKernelGGL(ms_trim_kernel, dim3((unsigned)n_segments, 1), dim3(CT), 0, ctx->stream, t);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stage[1], ctx->stream));
+    P2S_TRY(st.time_end());
     P2S_TRY(st.down(means, d_means, (size_t)n_segments * 8));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipEventElapsedTime(&ctx->measure_kernel_ms, ctx->ev_stage[0], ctx->ev_stage[1]));
-    return P2S_OK;
+    return st.finish(P2S_TIMED_MEASURE);
 }
 
 int p2s_body_measure_host(p2s_ctx *ctx, int32_t n_files, const int64_t *n_rows, const int32_t *n_markers, const double *data,
@@ -616,7 +602,7 @@ int p2s_body_measure_host(p2s_ctx *ctx, int32_t n_files, const int64_t *n_rows, 
     for (size_t f = 0; f < nf; ++f) rows32[f] = (int32_t)n_rows[f];
     const size_t nt = tile_seg.size(), n = (size_t)N, M = ncol * n;
 
-    MsLayout sm;                                                  // what the host knows
+    Layout sm;                                                    // what the host knows
     const size_t o_tab = sm.add(nf * 8), o_row = sm.add(nf * 8), o_head = sm.add(nf * 8), o_thr = sm.add(nf * 8), o_n = sm.add(nf * 4),
                  o_k = sm.add(nf * 4), o_ns = sm.add(nf * 4), o_fl = sm.add(nf * 4), o_role = sm.add(nf * P2S_MEASURE_ROLES * 4), o_pair = sm.add(nf * np * 8),
                  o_ts = sm.add(nt * 4), o_ti = sm.add(nt * 4);
@@ -633,11 +619,11 @@ int p2s_body_measure_host(p2s_ctx *ctx, int32_t n_files, const int64_t *n_rows, 
     if (np) memcpy(host.data() + o_pair, pairs, nf * np * 8);
     memcpy(host.data() + o_ts, tile_seg.data(), nt * 4);
     memcpy(host.data() + o_ti, tile_idx.data(), nt * 4);
-    MsLayout fp;                                                  // doubles
+    Layout fp;                                                    // doubles
     const size_t o_speed = fp.add(n * 8), o_key1 = fp.add(n * 8), o_ang = fp.add(n * 8), o_vals = fp.add(M * 8), o_sorted = fp.add(M * 8), o_means = fp.add(nf * ncol * 8);
-    MsLayout rc;                                                  // the sort's records
+    Layout rc;                                                    // the sort's records
     const size_t o_k0 = rc.add(M * 8), o_k1 = rc.add(M * 8), o_i0 = rc.add(M * 4), o_i1 = rc.add(M * 4), o_ord3 = rc.add(M * 4);
-    MsLayout in;                                                  // counters first: one memset
+    Layout in;                                                    // counters first: one memset
     const size_t o_cnt = in.add(nf * 5 * 4), o_has = in.add(nf * np * 4);
     const size_t zero_bytes = in.bytes;
     const size_t o_ord1 = in.add(n * 4), o_ord2 = in.add(n * 4), o_pos = in.add(n * 4), o_frame = in.add(n * 4);
@@ -672,7 +658,7 @@ int p2s_body_measure_host(p2s_ctx *ctx, int32_t n_files, const int64_t *n_rows, 
     s.idx[0] = (uint32_t *)(d_rc + o_i0); s.idx[1] = (uint32_t *)(d_rc + o_i1);
     const dim3 tiles((unsigned)nt), files((unsigned)n_files);
     hipStream_t q = ctx->stream;
-    HIP_TRY(hipEventRecord(ctx->ev_stage[0], q));
+    P2S_TRY(st.time_begin());
     hipLaunchKernelGGL(ms_speed_kernel, tiles, dim3(SB), 0, q, a);
     s.src = a.key1; s.seg_len = a.n_rows; s.order = a.order1; s.sorted = nullptr;
     HIP_TRY(p2s_launch_sort(s, (int64_t)nt, 1, longest, q));
@@ -691,7 +677,7 @@ int p2s_body_measure_host(p2s_ctx *ctx, int32_t n_files, const int64_t *n_rows, 
     t.vals = a.vals; t.sorted = a.sorted; t.row_off = a.row_off; t.seg_len = a.n_kept; t.means = a.means; t.col_stride = N; t.half_trim = half_trim;
     hipLaunchKernelGGL(ms_trim_kernel, dim3((unsigned)n_files, (unsigned)ncol), dim3(CT), 0, q, t);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stage[1], q));
+    P2S_TRY(st.time_end());
     P2S_TRY(st.down(sum_speeds, a.speed, n * 8));
     P2S_TRY(st.down(angles, a.ang, n * 8));
     P2S_TRY(st.down(n_selected, a.n_sel, nf * 4));
@@ -702,16 +688,11 @@ int p2s_body_measure_host(p2s_ctx *ctx, int32_t n_files, const int64_t *n_rows, 
     P2S_TRY(st.down(row_heights, a.vals + np * n, n * 8));
     P2S_TRY(st.down(row_values, a.vals, M * 8));
     P2S_TRY(st.down(means, a.means, nf * ncol * 8));
-    HIP_TRY(hipStreamSynchronize(q));                             // `host` is host memory: alive until here
-    HIP_TRY(hipEventElapsedTime(&ctx->measure_kernel_ms, ctx->ev_stage[0], ctx->ev_stage[1]));
-    return P2S_OK;
+    return st.finish(P2S_TIMED_MEASURE);                          // `host` is host memory: alive until here
 }
 
 int p2s_measure_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) {
-    if (!ctx || !elapsed_ms) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
-    if (ctx->measure_kernel_ms < 0.0f) return p2s_set_error(P2S_ERR_INVALID_ARG, "none of p2s_stable_argsort_host, p2s_trimmed_means_host and p2s_body_measure_host has run on this context");
-    *elapsed_ms = ctx->measure_kernel_ms;
-    return P2S_OK;
+    return p2s_kernel_ms_query(ctx, P2S_TIMED_MEASURE, "none of p2s_stable_argsort_host, p2s_trimmed_means_host and p2s_body_measure_host", elapsed_ms);
 }
 
 }  // extern "C"

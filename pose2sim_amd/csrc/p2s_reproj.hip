@@ -115,7 +115,7 @@ int p2s_reproject_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_markers, const 
     if (!sizes) return p2s_set_error(P2S_ERR_INVALID_ARG, "null sizes");
     if (!uv) return p2s_set_error(P2S_ERR_INVALID_ARG, "null uv");
     const int64_t n_units = n_frames * (int64_t)n_markers;
-    ctx->reproj_kernel_ms = 0.0f;
+    ctx->kernel_ms[P2S_TIMED_REPROJ] = 0.0f;                      // nothing to project: the call has run, in no time
     if (n_units == 0) return P2S_OK;
     if (!Q) return p2s_set_error(P2S_ERR_INVALID_ARG, "null Q");
     if (n_units > ((int64_t)1 << 38) / n_cams) return p2s_set_error(P2S_ERR_INVALID_ARG, "%lld units x %d cameras is too large", (long long)n_units, n_cams);
@@ -145,21 +145,14 @@ int p2s_reproject_host(p2s_ctx *ctx, int64_t n_frames, int32_t n_markers, const 
     P2S_TRY(st.upload(a.Q, Q, q_b));
     P2S_TRY(st.alloc(a.uv, out_b));
     if (uv_raw) P2S_TRY(st.alloc(a.uv_raw, out_b));
-    HIP_TRY(hipEventRecord(ctx->ev_stage[0], ctx->stream));
+    P2S_TRY(st.time_begin());
     HIP_TRY(p2s_launch_reproject(a, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_stage[1], ctx->stream));
+    P2S_TRY(st.time_end());
     P2S_TRY(st.down(uv, a.uv, out_b));
     P2S_TRY(st.down(uv_raw, a.uv_raw, out_b));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));          // `cams` is pageable host memory: alive until here
-    HIP_TRY(hipEventElapsedTime(&ctx->reproj_kernel_ms, ctx->ev_stage[0], ctx->ev_stage[1]));
-    return P2S_OK;
+    return st.finish(P2S_TIMED_REPROJ);                  // `cams` is pageable host memory: alive until here
 }
 
-int p2s_reproject_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) {
-    if (!ctx || !elapsed_ms) return p2s_set_error(P2S_ERR_INVALID_ARG, "null argument");
-    if (ctx->reproj_kernel_ms < 0.0f) return p2s_set_error(P2S_ERR_INVALID_ARG, "p2s_reproject_host has not run on this context");
-    *elapsed_ms = ctx->reproj_kernel_ms;
-    return P2S_OK;
-}
+int p2s_reproject_kernel_ms(p2s_ctx *ctx, float *elapsed_ms) { return p2s_kernel_ms_query(ctx, P2S_TIMED_REPROJ, "p2s_reproject_host", elapsed_ms); }
 
 }  // extern "C"

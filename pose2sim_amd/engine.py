@@ -34,6 +34,61 @@ def _entry(lib, name):
     return fn
 
 
+def _kernel_ms(self, name):
+    """What p2s_<name>_kernel_ms answers for the engine `self`: the kernel time of that stage's last call, from the HIP
+    events around its kernels."""
+    ms = C.c_float(0)
+    _lib.check(_entry(self._lib, f'p2s_{name}_kernel_ms')(self._h, C.byref(ms)))
+    return ms.value
+
+
+def _matrix(data):
+    """data as a contiguous float64 [n_frames][n_cols] matrix."""
+    data = np.ascontiguousarray(data, dtype=np.float64)
+    if data.ndim != 2:
+        raise P2sError(f'data has shape {data.shape}; expected [n_frames][n_cols]')
+    return data
+
+
+def _coeffs(b, a, zi):
+    """Filter coefficients b, a and the start state zi (scipy.signal.lfilter_zi) as contiguous float64 vectors."""
+    b, a, zi = (np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (b, a, zi))
+    if len(a) != len(b) or len(zi) != len(b) - 1:
+        raise P2sError('b, a and zi must have n, n and n - 1 coefficients')
+    return b, a, zi
+
+
+def _offsets(lengths):
+    """[0, lengths[0], lengths[0] + lengths[1], ...] as int64: where every run of `lengths` starts, and the total."""
+    return np.concatenate([[0], np.cumsum(lengths, dtype=np.int64)])
+
+
+def _per(values, n, dtype=np.float64):
+    """One value, or one per item, as a contiguous vector of n."""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(values, dtype=dtype), (n,)))
+
+
+def _pack_persons(cameras, n_kpts):
+    """cameras: per camera (persons [N][n_kpts][3], offsets [n_frames + 1]) -> (persons, offsets) per camera as checked
+    arrays, n_frames [C], base [C + 1] the cameras' first persons, off [frames + 1] the first person of every frame among
+    all persons, flat: the persons of all cameras back to back."""
+    persons, offsets = [], []
+    for p, o in cameras:
+        p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, n_kpts, 3)
+        o = np.ascontiguousarray(o, dtype=np.int64).reshape(-1)
+        if len(o) < 1 or o[0] != 0 or o[-1] != len(p) or (np.diff(o) < 0).any():
+            raise P2sError('offsets must rise from 0 to the number of persons')
+        persons.append(p)
+        offsets.append(o)
+    if len(persons) < 1:
+        raise P2sError('at least one camera is required')
+    n_frames = np.array([len(o) - 1 for o in offsets], dtype=np.int64)
+    base = _offsets([len(p) for p in persons])
+    off = np.concatenate([o[:-1] + b for o, b in zip(offsets, base[:-1])] + [base[-1:]]).astype(np.int64)
+    flat = persons[0] if len(persons) == 1 else np.concatenate(persons)
+    return persons, offsets, n_frames, base, off, flat
+
+
 def loess_window(nb_values_used):
     """(k, min_run) of the reference's loess filter for its nb_values_used: statsmodels' lowess takes
     k = int(frac * n + 1e-10) neighbours with frac = nb / n, and the reference filters the runs with len > nb
@@ -85,8 +140,7 @@ def write_openpose_files(cam_dirs, name_root, uv, marker_index=None, n_threads=0
     Cn, F, K = uv.shape[:3]
     idx = np.arange(K, dtype=np.int32) if marker_index is None else np.ascontiguousarray(marker_index, dtype=np.int32).reshape(-1)
     names = [os.fsencode(d) for d in cam_dirs]
-    offsets = np.zeros(Cn + 1, dtype=np.int64)
-    np.cumsum([len(n) for n in names], out=offsets[1:])
+    offsets = _offsets([len(n) for n in names])
     done = C.c_int64(0)
     _lib.check(fn(b''.join(names), _ptr(offsets), os.fsencode(name_root), Cn, F, K, len(idx), _optr(idx), _optr(uv),
                   int(n_threads), C.byref(done)))
@@ -243,13 +297,8 @@ class Engine:
     # -- downstream of the .trc -----------------------------------------
     def butterworth(self, data, b, a, zi):
         """Zero-phase Butterworth filter of every column of data [n_frames][n_cols] (filtering.py:437-471)."""
-        data = np.ascontiguousarray(data, dtype=np.float64)
-        if data.ndim != 2:
-            raise P2sError(f'data has shape {data.shape}; expected [n_frames][n_cols]')
-        b = np.ascontiguousarray(b, dtype=np.float64); a = np.ascontiguousarray(a, dtype=np.float64)
-        zi = np.ascontiguousarray(zi, dtype=np.float64)
-        if len(a) != len(b) or len(zi) != len(b) - 1:
-            raise P2sError('b, a and zi must have n, n and n - 1 coefficients')
+        data = _matrix(data)
+        b, a, zi = _coeffs(b, a, zi)
         out = np.empty_like(data)
         _lib.check(self._lib.p2s_butterworth_host(self._h, data.shape[0], data.shape[1], _optr(data), len(b), _ptr(b), _ptr(a),
                                                   _ptr(zi), _optr(out)))
@@ -259,9 +308,7 @@ class Engine:
         """One of the window / recurrence filters of filtering.py on every column of data [n_frames][n_cols]
         (include/p2s.h: P2S_FILTER_HAMPEL = 1, _GAUSSIAN = 2, _MEDIAN = 3, _ONE_EURO = 4, _KALMAN = 5, with their
         parameters)."""
-        data = np.ascontiguousarray(data, dtype=np.float64)
-        if data.ndim != 2:
-            raise P2sError(f'data has shape {data.shape}; expected [n_frames][n_cols]')
+        data = _matrix(data)
         params = np.ascontiguousarray(params, dtype=np.float64).reshape(-1)
         out = np.empty_like(data)
         _lib.check(self._lib.p2s_filter_columns_host(self._h, int(kind), data.shape[0], data.shape[1], _optr(data), _optr(params),
@@ -279,9 +326,7 @@ class Engine:
         raise what the reference raises: ValueError (a run of 2 to 4 samples, an ill-posed problem, a search without a
         minimum, a negative lambda), numpy.linalg.LinAlgError (a singular system)."""
         fn = _entry(self._lib, 'p2s_gcv_spline_host')
-        data = np.ascontiguousarray(data, dtype=np.float64)
-        if data.ndim != 2:
-            raise P2sError(f'data has shape {data.shape}; expected [n_frames][n_cols]')
+        data = _matrix(data)
         auto = cutoff == 'auto'
         lam = 0.0 if auto else float((frame_rate / (2 * np.pi * float(cutoff))) ** 4)     # filtering.py:301
         out = np.empty_like(data)
@@ -302,9 +347,7 @@ class Engine:
         frac = nb_values_used / len(run), it = 0 -- and every other sample is copied.  nb_values_used < 2 raises
         ValueError: a window of one sample has radius 0."""
         fn = _entry(self._lib, 'p2s_loess_host')
-        data = np.ascontiguousarray(data, dtype=np.float64)
-        if data.ndim != 2:
-            raise P2sError(f'data has shape {data.shape}; expected [n_frames][n_cols]')
+        data = _matrix(data)
         k, min_run = loess_window(nb_values_used)
         out = np.empty_like(data)
         _lib.check(fn(self._h, data.shape[0], data.shape[1], _optr(data), k, min_run, _optr(out)))
@@ -367,10 +410,7 @@ class Engine:
 
     def reproject_kernel_ms(self):
         """Kernel time of the last reproject() call, from HIP events around it."""
-        fn = _entry(self._lib, 'p2s_reproject_kernel_ms')
-        ms = C.c_float(0)
-        _lib.check(fn(self._h, C.byref(ms)))
-        return ms.value
+        return _kernel_ms(self, 'reproject')
 
     def write_openpose_files(self, cam_dirs, name_root, uv, marker_index=None, n_threads=0):
         return write_openpose_files(cam_dirs, name_root, uv, marker_index, n_threads)
@@ -419,7 +459,7 @@ class Engine:
             if found.value <= capacity:
                 break
             capacity = found.value                                # a second call with room for every event
-        f_off = np.concatenate([[0], np.cumsum(n_frames)])
+        f_off = _offsets(n_frames)
         r_off = f_off - np.arange(Cn + 1)
         out = {'displacements': [], 'bb_areas': [], 'jitter_mask': [], 'medians': list(med), 'thresholds': list(thr),
                'median_bb_area': [float(v) for v in med_area], 'counts': list(counts), 'events': events[:found.value]}
@@ -432,10 +472,7 @@ class Engine:
 
     def jitter_kernel_ms(self):
         """Kernel time of the last jitter() call, from HIP events around its kernels."""
-        fn = _entry(self._lib, 'p2s_jitter_kernel_ms')
-        ms = C.c_float(0)
-        _lib.check(fn(self._h, C.byref(ms)))
-        return ms.value
+        return _kernel_ms(self, 'jitter')
 
     # -- scipy.signal.find_peaks; gait contact signals (Utilities/trc_gaitevents.py) ---------------------------------------
     def find_peaks(self, data, prominence=None):
@@ -449,7 +486,7 @@ class Engine:
             raise P2sError(f'data has shape {data.shape}; expected [n_rows >= 1][n_cols >= 1]')
         cols = np.ascontiguousarray(data.T)                       # the library takes the columns contiguous
         n_cols, n_rows = cols.shape
-        bound = None if prominence is None else np.ascontiguousarray(np.broadcast_to(np.asarray(prominence, dtype=np.float64), (n_cols,)))
+        bound = None if prominence is None else _per(prominence, n_cols)
         capacity = min(max(cols.size // 16, 64), 1 << 22)
         counts, found = np.zeros(n_cols, dtype=np.int32), C.c_int64(0)
         while True:
@@ -460,7 +497,7 @@ class Engine:
             if found.value <= capacity:
                 break
             capacity = found.value                                # a second call with room for every peak
-        off = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+        off = _offsets(counts)
         return [(peaks[off[c]:off[c + 1]], prom[off[c]:off[c + 1]], lb[off[c]:off[c + 1]], rb[off[c]:off[c + 1]]) for c in range(n_cols)]
 
     GAIT_METHODS = {'height_coordinates': 0, 'forward_velocity': 1}
@@ -484,13 +521,10 @@ class Engine:
             raise P2sError('gait_contacts: at least one column, every column with at least one sample')
         lens = np.array([len(c) for c in columns], dtype=np.int64)
         max_rows = int(lens.max())
-        per_col = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)))   # noqa: E731
-        dt, threshold, factor = per_col(dt), per_col(threshold), per_col(factor)
+        dt, threshold, factor = _per(dt, n), _per(threshold, n), _per(factor, n)
         n_coef = n_w = 0
         if m == 0:
-            b, a, zi = (np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (b, a, zi))
-            if len(a) != len(b) or len(zi) != len(b) - 1:
-                raise P2sError('b, a and zi must have n, n and n - 1 coefficients')
+            b, a, zi = _coeffs(b, a, zi)
             n_coef = len(b)
             if int(lens.min()) - 1 <= 3 * n_coef:                 # scipy.signal.filtfilt's own refusal (_validate_pad)
                 raise ValueError(f'The length of the input vector x must be greater than padlen, which is {3 * n_coef}.')
@@ -518,10 +552,7 @@ class Engine:
 
     def gait_kernel_ms(self):
         """Kernel time of the last find_peaks() or gait_contacts() call, from HIP events around its kernels."""
-        fn = _entry(self._lib, 'p2s_gait_kernel_ms')
-        ms = C.c_float(0)
-        _lib.check(fn(self._h, C.byref(ms)))
-        return ms.value
+        return _kernel_ms(self, 'gait')
 
     # -- stable sort, trimmed means, body measurements (common.py:378-455, :715-1034) ---------------------------------------
     @staticmethod
@@ -538,7 +569,7 @@ class Engine:
         columns, lens, data = self._segments(columns, 'stable_argsort')
         order = np.empty(len(data), dtype=np.int32)
         _lib.check(fn(self._h, len(columns), _ptr(lens), _ptr(data), _ptr(order)))
-        off = np.concatenate([[0], np.cumsum(lens)])
+        off = _offsets(lens)
         return [order[off[c]:off[c + 1]].astype(np.int64) for c in range(len(columns))]
 
     def trimmed_means(self, columns, trimmed_extrema_percent=0.5):
@@ -575,10 +606,9 @@ class Engine:
         roles = np.ascontiguousarray(marker_index, dtype=np.int32).reshape(nf, len(_lib.P2S_MEASURE_ROLES))
         pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(nf, -1, 2)
         n_pairs = pairs.shape[1]
-        flags = np.ascontiguousarray(np.broadcast_to(np.asarray(flags, dtype=np.int32), (nf,)))
-        per_file = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (nf,)))   # noqa: E731
-        thr, head = per_file(close_to_zero_speed), per_file(head_factor)
-        n_speed = None if n_speed_markers is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_speed_markers, dtype=np.int32), (nf,)))
+        flags = _per(flags, nf, np.int32)
+        thr, head = _per(close_to_zero_speed, nf), _per(head_factor, nf)
+        n_speed = None if n_speed_markers is None else _per(n_speed_markers, nf, np.int32)
         data = np.concatenate([t.reshape(-1) for t in tables])
         N, ncol = int(n_rows.sum()), n_pairs + 2
         speeds, angles, heights = np.empty(N), np.empty(N), np.empty(N)
@@ -590,7 +620,7 @@ class Engine:
                       _ptr(thr), _ptr(n_speed), 1 - float(fastest_frames_to_remove_percent), float(large_hip_knee_angles),
                       float(trimmed_extrema_percent) / 2, _ptr(speeds), _ptr(angles), _ptr(n_sel), _ptr(pos), _ptr(frame),
                       _ptr(n_kept), _ptr(branch), _ptr(heights), _ptr(values), _ptr(means)))
-        off = np.concatenate([[0], np.cumsum(n_rows)])
+        off = _offsets(n_rows)
         out = []
         for f in range(nf):
             o, k = off[f], int(n_kept[f])
@@ -610,10 +640,7 @@ class Engine:
     def measure_kernel_ms(self):
         """Kernel time of the last stable_argsort(), trimmed_means() or body_measure() call, from HIP events around its
         kernels."""
-        fn = _entry(self._lib, 'p2s_measure_kernel_ms')
-        ms = C.c_float(0)
-        _lib.check(fn(self._h, C.byref(ms)))
-        return ms.value
+        return _kernel_ms(self, 'measure')
 
     # -- np.mean / np.std of columns; 2D confidence statistics (Utilities/pose_confidence_analyze.py:118-219) ------------
     def column_mean_std(self, data):
@@ -662,10 +689,7 @@ class Engine:
 
     def confidence_kernel_ms(self):
         """Kernel time of the last confidence_stats() call, from HIP events around its kernels."""
-        fn = _entry(self._lib, 'p2s_confidence_kernel_ms')
-        ms = C.c_float(0)
-        _lib.check(fn(self._h, C.byref(ms)))
-        return ms.value
+        return _kernel_ms(self, 'confidence')
 
     # -- linear_sum_assignment; frame-to-frame person matching (Utilities/id_switch_analyze.py:47-145, 148-291, 364-388) --
     def lsap(self, cost):
@@ -699,29 +723,15 @@ class Engine:
         not matched: 1 / 2 scipy's refusals (_lib.P2S_LSAP_ERRORS), 4 more than 32 kept persons), 'distances' the matched
         costs in frame and previous-person order, 'kept' the indices of the kept persons in order; and 'stats' [C][6] (ID_SWITCH_STATS; NaN without distances)."""
         fn = _entry(self._lib, 'p2s_id_switch_host')
-        persons, offsets = [], []
-        for p, o in cameras:
-            p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 26, 3)
-            o = np.ascontiguousarray(o, dtype=np.int64).reshape(-1)
-            if len(o) < 1 or o[0] != 0 or o[-1] != len(p) or (np.diff(o) < 0).any():
-                raise P2sError('offsets must rise from 0 to the number of persons')
-            persons.append(p)
-            offsets.append(o)
-        Cn = len(persons)
-        if Cn < 1:
-            raise P2sError('at least one camera is required')
-        n_frames = np.array([len(o) - 1 for o in offsets], dtype=np.int64)
-        base = np.concatenate([[0], np.cumsum([len(p) for p in persons])])
-        off = np.concatenate([o[:-1] + b for o, b in zip(offsets, base[:-1])] + [base[-1:]]).astype(np.int64)
-        flat = persons[0] if Cn == 1 else np.concatenate(persons)
-        frames, N = int(n_frames.sum()), int(base[-1])
+        persons, offsets, n_frames, base, off, flat = _pack_persons(cameras, 26)
+        Cn, frames, N = len(persons), int(n_frames.sum()), int(base[-1])
         tables = np.zeros((len(self.ID_SWITCH_TABLES), frames), dtype=np.int32)
         dist, n_dist, stats = np.empty(N), np.zeros(Cn, dtype=np.int64), np.empty((Cn, len(self.ID_SWITCH_STATS)))
         slots = np.zeros(N, dtype=np.int32)
         _lib.check(fn(self._h, Cn, _ptr(n_frames), _ptr(off), _optr(flat), _optr(tables), _optr(slots), _optr(dist), _ptr(n_dist),
                       _ptr(stats)))
-        f_off = np.concatenate([[0], np.cumsum(n_frames)])
-        d_off = np.concatenate([[0], np.cumsum(n_dist)])
+        f_off = _offsets(n_frames)
+        d_off = _offsets(n_dist)
         out = {name: [tables[i, f_off[c]:f_off[c + 1]] for c in range(Cn)] for i, name in enumerate(self.ID_SWITCH_TABLES)}
         out['kept'] = []
         for c in range(Cn):                                       # the frames' runs of kept persons -> one rising index list
@@ -735,10 +745,7 @@ class Engine:
 
     def id_switch_kernel_ms(self):
         """Kernel time of the last id_switch() call, from HIP events around its kernels."""
-        fn = _entry(self._lib, 'p2s_id_switch_kernel_ms')
-        ms = C.c_float(0)
-        _lib.check(fn(self._h, C.byref(ms)))
-        return ms.value
+        return _kernel_ms(self, 'id_switch')
 
     # -- primary-person selection (Utilities/pose_extract_person.py:37-87) --------------------------------------------------
     def track_select(self, cameras, n_kpts=26, conf_threshold=0.1):
@@ -750,34 +757,17 @@ class Engine:
         candidates in a frame are refused."""
         fn = _entry(self._lib, 'p2s_track_select_host')
         n_kpts = int(n_kpts)
-        persons, offsets = [], []
-        for p, o in cameras:
-            p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, max(n_kpts, 1), 3)
-            o = np.ascontiguousarray(o, dtype=np.int64).reshape(-1)
-            if len(o) < 1 or o[0] != 0 or o[-1] != len(p) or (np.diff(o) < 0).any():
-                raise P2sError('offsets must rise from 0 to the number of persons')
-            persons.append(p)
-            offsets.append(o)
-        Cn = len(persons)
-        if Cn < 1:
-            raise P2sError('at least one camera is required')
-        n_frames = np.array([len(o) - 1 for o in offsets], dtype=np.int64)
-        base = np.concatenate([[0], np.cumsum([len(p) for p in persons])])
-        off = np.concatenate([o[:-1] + b for o, b in zip(offsets, base[:-1])] + [base[-1:]]).astype(np.int64)
-        flat = persons[0] if Cn == 1 else np.concatenate(persons)
-        frames = int(n_frames.sum())
+        persons, _, n_frames, _, off, flat = _pack_persons(cameras, max(n_kpts, 1))
+        Cn, frames = len(persons), int(n_frames.sum())
         tables = np.zeros((3, frames), dtype=np.int32)
         _lib.check(fn(self._h, Cn, _ptr(n_frames), _ptr(off), _optr(flat), n_kpts, float(conf_threshold), _optr(tables[0]),
                       _optr(tables[1]), _optr(tables[2])))
-        f_off = np.concatenate([[0], np.cumsum(n_frames)])
+        f_off = _offsets(n_frames)
         return {name: [tables[i, f_off[c]:f_off[c + 1]] for c in range(Cn)] for i, name in enumerate(('chosen', 'n_candidates', 'prev'))}
 
     def track_select_kernel_ms(self):
         """Kernel time of the last track_select() call, from HIP events around its kernels."""
-        fn = _entry(self._lib, 'p2s_track_select_kernel_ms')
-        ms = C.c_float(0)
-        _lib.check(fn(self._h, C.byref(ms)))
-        return ms.value
+        return _kernel_ms(self, 'track_select')
 
     # -- synchronization (synchronization.py:1271-1343, 1541-1585) -------------------------------------------------------
     def sync_speeds(self, coords, b, a, zi):
@@ -793,10 +783,7 @@ class Engine:
         n_cols = cols[0].shape[1] if cols else 0
         lens = np.array([c.shape[0] for c in cols], dtype=np.int64)
         flat = np.ascontiguousarray(np.concatenate([c.reshape(-1) for c in cols])) if cols else np.zeros(0)
-        b = np.ascontiguousarray(b, dtype=np.float64); a = np.ascontiguousarray(a, dtype=np.float64)
-        zi = np.ascontiguousarray(zi, dtype=np.float64)
-        if len(a) != len(b) or len(zi) != len(b) - 1:
-            raise P2sError('b, a and zi must have n, n and n - 1 coefficients')
+        b, a, zi = _coeffs(b, a, zi)
         out = np.empty(int(lens.sum()), dtype=np.float64)
         rc = fn(self._h, len(cols), _optr(lens), n_cols, _optr(flat), len(b), _ptr(b), _ptr(a), _ptr(zi), _optr(out))
         if rc == _lib.P2S_ERR_SYNC_PADLEN:
@@ -836,8 +823,7 @@ class Engine:
             raise P2sError(f'n_persons has {Cn} cameras; calibration has {self.n_cams}')
         kpts, dtype = as_packed(kpts)
         per_frame = n_persons.sum(axis=1, dtype=np.int64)
-        offsets = np.zeros(F + 1, dtype=np.int64)
-        np.cumsum(per_frame, out=offsets[1:])
+        offsets = _offsets(per_frame)
         if kpts.ndim != 3 or kpts.shape[0] != offsets[-1] or kpts.shape[2] != 3:
             raise P2sError(f'kpts has shape {kpts.shape}; expected [{offsets[-1]}, Kj, 3]')
         n_max = int(per_frame.max()) if F else 0
@@ -856,8 +842,7 @@ class Engine:
         if Cn != self.n_cams:
             raise P2sError(f'n_persons has {Cn} cameras; calibration has {self.n_cams}')
         tracked, dtype = as_packed(np.asarray(tracked).reshape(-1, 3))
-        offsets = np.zeros(F + 1, dtype=np.int64)
-        np.cumsum(n_persons.sum(axis=1, dtype=np.int64), out=offsets[1:])
+        offsets = _offsets(n_persons.sum(axis=1, dtype=np.int64))
         if tracked.shape[0] != offsets[-1]:
             raise P2sError(f'tracked has {tracked.shape[0]} rows; n_persons sums to {offsets[-1]}')
         comb = np.full((F, Cn), -1, dtype=np.int32)

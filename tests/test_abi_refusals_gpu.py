@@ -26,6 +26,7 @@ OUT = np.empty(64)                                                  # room for a
 IOUT = np.empty(64, dtype=np.int64)
 IDS_OUT = (P(IOUT), P(IOUT), P(OUT), P(IOUT), P(OUT))                # tables, kept, distances, n_distances, stats
 CONF_OUT = (P(OUT), P(IOUT), P(IOUT), P(IOUT))                      # stats, counts, below, bands
+TS_OUT = (P(IOUT), P(IOUT), P(IOUT))                                # chosen, n_candidates, prev
 
 # (entry point, arguments after the context, return code, message)
 CASES = [
@@ -90,6 +91,23 @@ CASES = [
     ('p2s_column_mean_std_host', (2 ** 31, 2, P(f8(2, 4)), P(OUT), P(OUT), P(IOUT)), INVALID, 'bad shape: 2147483648 rows, 2 columns'),
     ('p2s_column_mean_std_host', (4, -1, P(f8(2, 4)), P(OUT), P(OUT), P(IOUT)), INVALID, 'bad shape: 4 rows, -1 columns'),
     ('p2s_column_mean_std_host', (4, 2, None, P(OUT), P(OUT), P(IOUT)), INVALID, 'null argument'),
+    # (new cases go at the end: a case's position is part of its test id)
+    # p2s_track_select_host(n_cams, n_frames, person_off, persons, n_kpts, conf_threshold, chosen, n_candidates, prev): the frame
+    # and person offsets are id_switch's, with its messages
+    ('p2s_track_select_host', (0, P(i8(1)), P(i8(0, 1)), P(f8(1, 26, 3)), 26, 0.1) + TS_OUT, INVALID, 'n_cams=0 outside [1, 65535]'),
+    ('p2s_track_select_host', (65536, P(i8(1)), P(i8(0, 1)), P(f8(1, 26, 3)), 26, 0.1) + TS_OUT, INVALID, 'n_cams=65536 outside [1, 65535]'),
+    ('p2s_track_select_host', (1, P(i8(1)), P(i8(0, 1)), P(f8(1, 26, 3)), 0, 0.1) + TS_OUT, INVALID, 'n_kpts=0 outside [1, 127]'),
+    ('p2s_track_select_host', (1, P(i8(1)), P(i8(0, 1)), P(f8(1, 128, 3)), 128, 0.1) + TS_OUT, INVALID, 'n_kpts=128 outside [1, 127]'),
+    ('p2s_track_select_host', (1, None, P(i8(0, 1)), P(f8(1, 26, 3)), 26, 0.1) + TS_OUT, INVALID, 'null argument'),
+    ('p2s_track_select_host', (1, P(i8(1)), None, P(f8(1, 26, 3)), 26, 0.1) + TS_OUT, INVALID, 'null argument'),
+    ('p2s_track_select_host', (1, P(i8(-1)), P(i8(0, 1)), P(f8(1, 26, 3)), 26, 0.1) + TS_OUT, INVALID, 'camera 0 has -1 frames; expected 0 .. 2^31 - 1'),
+    ('p2s_track_select_host', (2, P(i8(1, 2 ** 31)), P(i8(0, 1)), P(f8(1, 26, 3)), 26, 0.1) + TS_OUT, INVALID,
+     'camera 1 has 2147483648 frames; expected 0 .. 2^31 - 1'),
+    ('p2s_track_select_host', (2, P(i8(2 ** 31 - 1, 1)), P(i8(0, 1)), P(f8(1, 26, 3)), 26, 0.1) + TS_OUT, INVALID, '2147483648 frames are too many'),
+    ('p2s_track_select_host', (1, P(i8(1)), P(i8(1, 2)), P(f8(2, 26, 3)), 26, 0.1) + TS_OUT, INVALID, 'person_off must start at 0'),
+    ('p2s_track_select_host', (1, P(i8(2)), P(i8(0, 2, 1)), P(f8(2, 26, 3)), 26, 0.1) + TS_OUT, INVALID, 'person_off must not decrease (frame 1)'),
+    ('p2s_track_select_host', (1, P(i8(1)), P(i8(0, 2 ** 31)), P(f8(1, 26, 3)), 26, 0.1) + TS_OUT, INVALID, '2147483648 persons are too many'),
+    ('p2s_track_select_host', (1, P(i8(1)), P(i8(0, 1)), None, 26, 0.1) + TS_OUT, INVALID, 'null argument'),
 ]
 KEEP = [B, A, ZI, A_BAD, NAN_DATA, SHORT_RUN, INF_RUN, OUT, IOUT]    # the temporaries above are kept alive by ctypes' own references
 
@@ -134,37 +152,50 @@ def test_lsap_refuses_a_bad_shape(lib, ctx):
 
 
 def test_kernel_times_refuse_until_their_own_stage_has_run(lib):
-    """The four stages that time their kernels share one pair of events; each query still answers for its own stage."""
+    """The seven stages that time their kernels share one pair of events; each query still answers for its own stage alone,
+    and for gait and measure, which keep several entry points behind one query, any of them arms it."""
     from pose2sim_amd.engine import Engine
     P34 = np.array([[[1000.0, 0, 960, 0], [0, 1000.0, 540, 0], [0, 0, 1, 4.0]]])
-    # (the query, the entry point its refusal names, a small call of that stage)
-    stages = (('p2s_reproject_kernel_ms', 'p2s_reproject_host', lambda e: e.reproject(np.zeros((3, 2, 3)), P=P34, sizes=np.array([[1920.0, 1080.0]]))),
-              ('p2s_jitter_kernel_ms', 'p2s_jitter_host', lambda e: e.jitter([np.ones((4, 26, 3))])),
-              ('p2s_confidence_kernel_ms', 'p2s_confidence_stats_host', lambda e: e.confidence_stats([np.full((4, 26), 0.5)])),
-              ('p2s_id_switch_kernel_ms', 'p2s_id_switch_host', lambda e: e.id_switch([(np.full((2, 26, 3), 0.5), [0, 1, 2])])))
+    person = (np.full((2, 26, 3), 0.5), [0, 1, 2])                    # one camera of 2 frames with one person each
+    filt = dict(b=[0.5, 0.5], a=[1.0, 0.0], zi=[0.5])
+    table = np.arange(60.0).reshape(2, 30) % 7.0                     # 2 rows of 10 markers
+    # (the query, what its refusal names, the smallest call of every entry point of that stage)
+    stages = (('p2s_reproject_kernel_ms', 'p2s_reproject_host has not', (lambda e: e.reproject(np.zeros((3, 2, 3)), P=P34, sizes=np.array([[1920.0, 1080.0]])),)),
+              ('p2s_jitter_kernel_ms', 'p2s_jitter_host has not', (lambda e: e.jitter([np.ones((4, 26, 3))]),)),
+              ('p2s_confidence_kernel_ms', 'p2s_confidence_stats_host has not', (lambda e: e.confidence_stats([np.full((4, 26), 0.5)]),)),
+              ('p2s_id_switch_kernel_ms', 'p2s_id_switch_host has not', (lambda e: e.id_switch([person]),)),
+              ('p2s_gait_kernel_ms', 'neither p2s_find_peaks_host nor p2s_gait_contacts_host has',
+               (lambda e: e.find_peaks(np.array([[0.0], [1.0], [0.0], [2.0], [0.0]])),
+                lambda e: e.gait_contacts([np.arange(9.0)], 'height_coordinates', 1.0, 4.0, **filt))),
+              ('p2s_measure_kernel_ms', 'none of p2s_stable_argsort_host, p2s_trimmed_means_host and p2s_body_measure_host has',
+               (lambda e: e.stable_argsort([[2.0, 1.0, 3.0]]),
+                lambda e: e.trimmed_means([[2.0, 1.0, 3.0]]),
+                lambda e: e.body_measure([table], [[-1] * 10], np.zeros((1, 0, 2)), 0))),
+              ('p2s_track_select_kernel_ms', 'p2s_track_select_host has not', (lambda e: e.track_select([person]),)))
     ms = C.c_float(0)
     for query, _, _ in stages:
         assert getattr(lib, query)(None, C.byref(ms)) == INVALID and lib.p2s_last_error().decode() == 'null argument'
 
-    def refuses(eng, query, entry):
-        return getattr(lib, query)(eng._h, C.byref(ms)) == INVALID and lib.p2s_last_error().decode() == f'{entry} has not run on this context'
+    def refuses(eng, query, who):
+        return getattr(lib, query)(eng._h, C.byref(ms)) == INVALID and lib.p2s_last_error().decode() == f'{who} run on this context'
 
     def answers(eng, query):
         ms.value = -1.0
         return getattr(lib, query)(eng._h, C.byref(ms)) == 0 and ms.value >= 0.0
 
-    for first in range(len(stages)):                                 # every stage as the first one of a fresh context
-        eng = Engine(0)
-        assert all(refuses(eng, query, entry) for query, entry, _ in stages)
-        stages[first][2](eng)
-        assert answers(eng, stages[first][0])
-        for query, entry, _ in stages:                               # another stage's call does not count
-            assert query == stages[first][0] or refuses(eng, query, entry), (stages[first][0], query)
-        for n, (_, _, run) in enumerate(stages):                     # the others one by one: what has run answers, the rest refuses
-            if n != first:
-                run(eng)
-            done = set(range(n + 1)) | {first}
-            for k, (query, entry, _) in enumerate(stages):
-                assert answers(eng, query) if k in done else refuses(eng, query, entry), (first, n, query)
-        assert all(answers(eng, query) for query, _, _ in stages)
-        eng.close()
+    for first, (armed, _, runs) in enumerate(stages):
+        for run_first in runs:                                       # every entry point as the first call of a fresh context
+            eng = Engine(0)
+            assert all(refuses(eng, query, who) for query, who, _ in stages)
+            run_first(eng)
+            assert answers(eng, armed)
+            for query, who, _ in stages:                             # another stage's call does not count
+                assert query == armed or refuses(eng, query, who), (armed, query)
+            for n, (_, _, others) in enumerate(stages):              # the others one by one: what has run answers, the rest refuses
+                if n != first:
+                    others[-1](eng)
+                done = set(range(n + 1)) | {first}
+                for k, (query, who, _) in enumerate(stages):
+                    assert answers(eng, query) if k in done else refuses(eng, query, who), (first, n, query)
+            assert all(answers(eng, query) for query, _, _ in stages)
+            eng.close()

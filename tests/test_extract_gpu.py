@@ -46,6 +46,23 @@ def test_chain_lengths_around_the_tile(engine, F):
     check(engine, [cam])
 
 
+@pytest.mark.parametrize('F', [255, 256, 257, 513])
+def test_prev_across_the_edge_of_the_frame_tile(engine, F):
+    """The previous selecting frame comes from a scan in tiles of 256 frames (p2s_scan.h; id_switch runs the same kernels):
+    cameras that end before, on and one frame after a tile's edge and in a third tile.  Nobody is listed in frames 200 ..
+    249 nor from frame 253 to the last but one (at most to 511), so the answers lie in a frame's own tile, in the tile before
+    and, for 513 frames, two tiles back, past a tile without anybody.  A second, shorter camera goes in the same call: its
+    last tile is not the grid's."""
+    empty = [f for f in list(range(200, 250)) + list(range(253, min(F - 1, 512))) if f < F]
+    cams = [en.crowd_camera(F, 200 + F, 3, empty=empty), en.crowd_camera(F - 130, 201 + F, 2, empty=range(100, F - 131))]
+    got = check(engine, cams)
+    prev, n = got['prev'], got['n_candidates']
+    print(f'{F} and {F - 130} frames: prev[250] = {prev[0][250]}, prev of the last frames {prev[0][-1]} and {prev[1][-1]}, '
+          f'frames with a candidate {int((n[0] > 0).sum())} and {int((n[1] > 0).sum())}')
+    assert prev[0][250] == 199 and prev[0][-1] == 252 and n[0][-1] > 0
+    assert prev[1][-1] == 99 and n[1][-1] > 0
+
+
 def test_cameras_without_frames_and_without_candidates(engine):
     nobody = (np.zeros((0, 26, 3)), np.zeros(1, dtype=np.int64))
     weak = en.crowd_camera(2 * T + 5, 7, 3)
