@@ -402,6 +402,47 @@ int p2s_track_select_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *n_frames,
 /* Milliseconds the kernels of this context's last p2s_track_select_host took (HIP events around them). */
 int p2s_track_select_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
 
+/* ---- person tracking across frames (triangulation.py:823-874, sort_people_sports2d of common.py:1037-1136) ----------------
+ * Which detection every person slot of multi-person triangulation takes, frame after frame, for a batch of trials in one
+ * launch (one workgroup a trial, the loop over its frames inside it).  float64 and bit for bit the reference's numbers.
+ * The trials share n_persons (P, 1 .. 32) and n_kpts (K >= 1) and stand back to back: Q [N][P][K][3] (NaN = not
+ * triangulated), frame_off [n_trials + 1] with frame_off[0] = 0, first_frame [n_trials] the absolute number of every
+ * trial's first frame.  A trial keeps a state S [32][K][3], the last non-NaN value of every coordinate of every slot, n of
+ * its rows live; it starts as P rows of NaN, or as the first n_state_in[t] rows (0 .. 32) of state_in [n_trials][32][K][3]
+ * -- the state_out and n_state_out of an earlier call, which continues a trial in chunks.  Per frame: the n x P matrix of
+ * mean keypoint distances (np.sqrt(np.nansum(diff**2)) per keypoint, np.nanmean over them in NumPy's summation order, NaN
+ * and +inf as 1e10), p2s_lsap_host's assignment on it, with has_max_dist the pairs above max_dist dropped, the detections
+ * left over as new slots n, n + 1, ... in ascending order, and S takes the placed detections' non-NaN values.  The
+ * absolute frame 0 (and a state without rows) is not matched: detection p goes to slot p.  Outputs, each may be NULL
+ * but status:
+ *   ids [N][P] int32          the detection the first P slots took, -1 for none
+ *   Q_rows [N][P][K][3]       the points in tracked order, NaN for a slot without a detection
+ *   matched_dist [N][P]       the distance of the kept pair of every slot; NaN without one and in a frame not matched
+ *   n_slots [N] int32         slots after the frame
+ *   state_out [n_trials][32][K][3], n_state_out [n_trials] int32    the state after the trial's last frame
+ *   status [n_trials][2] int32   0, 0; or the first frame (trial-local, plus 1) that would have passed 32 slots, and in
+ *                             the second word what p2s_lsap_host's status says when that frame's matrix was refused
+ *                             instead (-1: a slot count outside 0 .. 32 read on the device); nothing from that frame on
+ *                             is defined for the trial
+ * The workgroup's LDS -- S, one frame, the cost matrix and at least one pair's K distances, (96 + 3 P + 1) K + 1 024
+ * doubles and 2 KB of the solver's and the placement's arrays -- must fit what the device gives a workgroup (queried), and K <= 240 there:
+ * P2S_ERR_INVALID_ARG otherwise, as for P outside 1 .. 32, nothing written.
+ * p2s_track_persons_host: HOST pointers; blocks.  ctx == NULL runs the same code on the host (no LDS limit): the
+ * restatement can be checked without a GPU.
+ * p2s_track_persons_device: Q, the states and every output are DEVICE pointers, frame_off and first_frame stay HOST
+ * arrays (the shape, copied before the call returns); enqueues on the context's stream and reads nothing back -- the call
+ * to chain after p2s_triangulate_device. */
+int p2s_track_persons_host(p2s_ctx *ctx, int64_t n_trials, const int64_t *frame_off, const int64_t *first_frame, int32_t n_persons,
+                           int32_t n_kpts, const double *Q, int32_t has_max_dist, double max_dist, const double *state_in,
+                           const int32_t *n_state_in, int32_t *ids, double *Q_rows, double *matched_dist, int32_t *n_slots,
+                           double *state_out, int32_t *n_state_out, int32_t *status);
+int p2s_track_persons_device(p2s_ctx *ctx, int64_t n_trials, const int64_t *frame_off, const int64_t *first_frame, int32_t n_persons,
+                             int32_t n_kpts, const double *d_Q, int32_t has_max_dist, double max_dist, const double *d_state_in,
+                             const int32_t *d_n_state_in, int32_t *d_ids, double *d_Q_rows, double *d_matched_dist, int32_t *d_n_slots,
+                             double *d_state_out, int32_t *d_n_state_out, int32_t *d_status);
+/* Milliseconds the kernel of this context's last p2s_track_persons_host took (HIP events around it). */
+int p2s_track_persons_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
+
 /* ---- find_peaks (scipy.signal, 1.15.3) -----------------------------------------------------------------------------------
  * scipy.signal.find_peaks(x, prominence=p) for each of n_cols contiguous float64 columns of n_rows entries (column-major,
  * as p2s_column_order_stats_host takes them), bit for bit: _local_maxima_1d (a plateau's peak is (left_edge + right_edge)

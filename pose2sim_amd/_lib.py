@@ -28,6 +28,7 @@ P2S_REPROJ_DISTORTED = 1
 P2S_TRACK_SELECTED, P2S_TRACK_NO_PEOPLE, P2S_TRACK_NO_CANDIDATE = 1, 0, 2
 P2S_TRACK_LONG_LIST, P2S_TRACK_BAD_FILE, P2S_TRACK_BAD_CONTENT = -1, -2, -3
 P2S_TRACK_MAX_CANDIDATES = 32
+P2S_TRACK_MAX_SLOTS = 32   # person slots of p2s_track_persons_*: the rows of its state
 P2S_TRACK_TILE = 32      # frames per tile of the map scan in csrc/p2s_extract.hip (T): tests place their cases around it
 (P2S_JSON_PERSON_ALL_INTS, P2S_JSON_PERSON_HAS_NULL, P2S_JSON_PERSON_HAS_BOOL, P2S_JSON_PERSON_BIG_INT, P2S_JSON_PERSON_NOT_OBJECT,
  P2S_JSON_PERSON_BAD_LIST) = 1, 2, 4, 8, 16, 32
@@ -114,6 +115,11 @@ SIGNATURES = {
     'p2s_id_switch_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     'p2s_track_select_host': (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_double] + [C.c_void_p] * 3),
     'p2s_track_select_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    'p2s_track_persons_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                        C.c_double] + [C.c_void_p] * 9),
+    'p2s_track_persons_device': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.c_double] + [C.c_void_p] * 9),
+    'p2s_track_persons_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     'p2s_json_person_flags': (C.c_int, [C.c_void_p, C.c_void_p]),
     'p2s_write_person_files': (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     'p2s_find_peaks_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]
@@ -159,7 +165,8 @@ OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_h
             'p2s_id_switch_host', 'p2s_id_switch_kernel_ms', 'p2s_json_person_ids', 'p2s_loess_host',
             'p2s_find_peaks_host', 'p2s_gait_contacts_host', 'p2s_gait_kernel_ms', 'p2s_stable_argsort_host',
             'p2s_trimmed_means_host', 'p2s_body_measure_host', 'p2s_measure_kernel_ms', 'p2s_track_select_host',
-            'p2s_track_select_kernel_ms', 'p2s_json_person_flags', 'p2s_write_person_files'}
+            'p2s_track_select_kernel_ms', 'p2s_json_person_flags', 'p2s_write_person_files', 'p2s_track_persons_host',
+            'p2s_track_persons_device', 'p2s_track_persons_kernel_ms'}
 
 _lib = None
 

@@ -147,6 +147,51 @@ def write_openpose_files(cam_dirs, name_root, uv, marker_index=None, n_threads=0
     return done.value
 
 
+class TrackShapeError(P2sError):
+    """p2s_track_persons_* refused the shape: persons outside 1 .. 32, or keypoints beyond what the device's LDS holds."""
+
+
+def _track_persons(lib, handle, Q, first_frame, max_dist, state):
+    """p2s_track_persons_host on `handle` (None: the library's host path) for one trial Q [F][P][K][3] or a list of
+    trials of one P and K; what Engine.track_persons_3d returns."""
+    fn = _entry(lib, 'p2s_track_persons_host')
+    single = not isinstance(Q, (list, tuple))
+    trials = [np.ascontiguousarray(q, dtype=np.float64) for q in ([Q] if single else Q)]
+    if not trials or any(q.ndim != 4 or q.shape[1:] != trials[0].shape[1:] or q.shape[3] != 3 for q in trials):
+        raise P2sError('every trial needs a [n_frames][n_persons][n_kpts][3] array with the same n_persons and n_kpts')
+    T, (P, K) = len(trials), trials[0].shape[1:3]
+    off = _offsets([len(q) for q in trials])
+    N = int(off[-1])
+    first = _per(first_frame, T, np.int64)
+    flat = trials[0] if T == 1 else np.concatenate(trials)
+    S = _lib.P2S_TRACK_MAX_SLOTS
+    state_in = n_in = None
+    if state is not None:
+        states = [np.asarray(s, dtype=np.float64).reshape(-1, K, 3) for s in ([state] if single else state)]
+        if len(states) != T or max(len(s) for s in states) > S:
+            raise P2sError(f'state: one [n <= {S}][n_kpts][3] array per trial')
+        n_in = np.array([len(s) for s in states], dtype=np.int32)
+        state_in = np.full((T, S, K, 3), np.nan)
+        for t, s in enumerate(states):
+            state_in[t, :len(s)] = s
+    ids, n_slots = np.empty((N, P), dtype=np.int32), np.empty(N, dtype=np.int32)
+    rows, dist = np.empty((N, P, K, 3)), np.empty((N, P))
+    state_out, n_out, status = np.empty((T, S, K, 3)), np.zeros(T, dtype=np.int32), np.zeros((T, 2), dtype=np.int32)
+    rc = fn(handle, T, _ptr(off), _ptr(first), P, K, _optr(flat), 0 if max_dist is None else 1, 0.0 if max_dist is None else float(max_dist),
+            _ptr(state_in), _ptr(n_in), _optr(ids), _optr(rows), _optr(dist), _optr(n_slots), _ptr(state_out), _ptr(n_out), _ptr(status))
+    if rc == _lib.P2S_ERR_INVALID_ARG:
+        raise TrackShapeError(f'p2s error {rc}: {lib.p2s_last_error().decode()}')
+    _lib.check(rc)
+    cut = lambda a: [a[off[t]:off[t + 1]] for t in range(T)]         # noqa: E731
+    out = (cut(rows), cut(ids), cut(dist), cut(n_slots), [state_out[t, :n_out[t]] for t in range(T)], list(status))
+    return tuple(o[0] for o in out) if single else out
+
+
+def track_persons_3d_host(Q, first_frame=0, max_dist=None, state=None):
+    """Engine.track_persons_3d by the library's host path (no context, no GPU): the same code, for checking it."""
+    return _track_persons(_lib.load(), None, Q, first_frame, max_dist, state)
+
+
 class Engine:
     def __init__(self, device=0):
         self._lib = _lib.load()
@@ -768,6 +813,38 @@ class Engine:
     def track_select_kernel_ms(self):
         """Kernel time of the last track_select() call, from HIP events around its kernels."""
         return _kernel_ms(self, 'track_select')
+
+    # -- person tracking across frames (triangulation.py:823-874, common.py:1037-1136) ---------------------------------------
+    def track_persons_3d(self, Q, first_frame=0, max_dist=None, state=None):
+        """Q: one trial [F][P][K][3] float64 of triangulated points (NaN = none), or a list of trials of one P <= 32 and K
+        (lengths may differ); first_frame: the absolute number of the trial's first frame (one, or one per trial: frame 0 is
+        not matched); max_dist: the reference's max_distance_m; state: the `state` of an earlier call ([n][K][3], n <= 32,
+        per trial), to continue a trial in chunks.  The reference's frame-by-frame sort_people_sports2d, every trial a
+        workgroup of one launch (csrc/p2s_track.hip).  -> (Q_rows [F][P][K][3] the points in tracked order, ids [F][P] int32
+        the detection every slot took or -1, matched_dist [F][P] the mean keypoint distance of every kept pair or NaN,
+        n_slots [F] int32, state [n][K][3], status [2] int32: zeros, or (the first frame, plus 1, that would have passed 32
+        slots, the assignment's refusal if that stopped it) -- nothing from that frame on is defined), each a list for a
+        list of trials.  A shape the kernel does not take raises TrackShapeError."""
+        return _track_persons(self._lib, self._h, Q, first_frame, max_dist, state)
+
+    def track_persons_3d_device(self, frame_off, first_frame, P, K, d_Q, max_dist=None, d_state_in=None, d_n_state_in=None, d_ids=None,
+                                d_Q_rows=None, d_matched_dist=None, d_n_slots=None, d_state_out=None, d_n_state_out=None, d_status=None):
+        """Device-resident form (tensors or raw pointers; frame_off [T + 1] and first_frame [T] are host int64 arrays):
+        enqueues on the engine's stream and reads nothing back -- d_Q may be what triangulate_device just filled.
+        d_status [T][2] int32 is required, every other output may be None."""
+        fn = _entry(self._lib, 'p2s_track_persons_device')
+        off = np.ascontiguousarray(frame_off, dtype=np.int64).reshape(-1)
+        first = _per(first_frame, max(len(off) - 1, 0), np.int64)
+        rc = fn(self._h, len(off) - 1, _ptr(off), _ptr(first), int(P), int(K), _ptr(d_Q), 0 if max_dist is None else 1,
+                0.0 if max_dist is None else float(max_dist), _ptr(d_state_in), _ptr(d_n_state_in), _ptr(d_ids), _ptr(d_Q_rows),
+                _ptr(d_matched_dist), _ptr(d_n_slots), _ptr(d_state_out), _ptr(d_n_state_out), _ptr(d_status))
+        if rc == _lib.P2S_ERR_INVALID_ARG:
+            raise TrackShapeError(f'p2s error {rc}: {self._lib.p2s_last_error().decode()}')
+        _lib.check(rc)
+
+    def track_persons_kernel_ms(self):
+        """Kernel time of the last track_persons_3d() call, from HIP events around its kernel."""
+        return _kernel_ms(self, 'track_persons')
 
     # -- synchronization (synchronization.py:1271-1343, 1541-1585) -------------------------------------------------------
     def sync_speeds(self, coords, b, a, zi):

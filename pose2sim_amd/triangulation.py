@@ -2,9 +2,10 @@
 (triangulation.py:656-959), with the per-(frame x person x keypoint) work on the MI355X.
 
 The frame / person / keypoint loops (triangulation.py:796-845) become ONE call into the HIP
-engine over the packed tensor of every frame; what stays on the host is what carries state
-from frame to frame: person tracking (:847-865), interpolation (:889-894), valid-section
-trimming (:897-919), gap filling (:922-926), the .trc writer (:929) and the recap log (:959).
+engine over the packed tensor of every frame, and person tracking across the frames (:847-865)
+one more; what stays on the host is the rest of the frame-sequential tail: interpolation
+(:889-894), valid-section trimming (:897-919), gap filling (:922-926), the .trc writer (:929)
+and the recap log (:959).
 There is no CPU fallback for the kernel work.
 """
 import logging
@@ -80,6 +81,23 @@ def track_persons(Q, f_range, multi_person, max_distance_m):
             ids[fi] = [int(sorted_ids[n]) for n in range(P)]
         Q_out[fi] = Q_cur[:P]
     return Q_out, ids
+
+
+def track_persons_engine(engine, Q, f_range, multi_person, max_distance_m):
+    """track_persons with the loop over the frames on the GPU (Engine.track_persons_3d, csrc/p2s_track.hip): the same
+    (Q_rows, ids), bit for bit.  The host loop takes over, silently, when the engine has no such call (a library built
+    before it, a test double), when the shape does not fit the kernel, and when a trial passes 32 person slots."""
+    track = getattr(engine, 'track_persons_3d', None)
+    if not multi_person or track is None or not len(Q):
+        return track_persons(Q, f_range, multi_person, max_distance_m)
+    from .engine import TrackShapeError
+    try:
+        Q_rows, ids, _, _, _, status = track(Q, first_frame=f_range[0], max_dist=max_distance_m)
+    except (NotImplementedError, TrackShapeError):
+        return track_persons(Q, f_range, multi_person, max_distance_m)
+    if np.any(status):
+        return track_persons(Q, f_range, multi_person, max_distance_m)
+    return Q_rows, ids.astype(np.int64)
 
 
 def in_tracked_order(table, ids, empty):
@@ -249,7 +267,7 @@ def triangulate_all(config_dict):
 
     def sequential_steps(Qk, err_frames, excl_frames):
         """Tracking, then per person interpolation, kept section, gap filling and the file (rank 0)."""
-        Q_rows, ids = track_persons(Qk, f_range, multi_person, max_distance_m)
+        Q_rows, ids = track_persons_engine(engine, Qk, f_range, multi_person, max_distance_m)
         e_fr = in_tracked_order(err_frames, ids, np.nan)
         x_fr = in_tracked_order(excl_frames, ids, float(n_cams))
         people = [finish_person(n, Q_rows[:, n].reshape(len(frames), keypoints_nb * 3), e_fr[:, n], x_fr[:, n], frames, settings,
