@@ -608,6 +608,8 @@ int p2s_get_assoc_stats(p2s_ctx *ctx, uint64_t *out, int32_t reset);
  *                         results)
  *   P2S_TUNE_ASSOC_FORM   P2S_ASSOC_FORM_AUTO (default): up to 32 detections per frame take the symmetric one-wave kernel;
  *                         P2S_ASSOC_FORM_GENERAL: the general kernel (no symmetry assumed) at every size
+ *   P2S_TUNE_GAPS_WORKSPACE_KB  cap (KiB, default P2S_GAPS_WORKSPACE_KB) of the spline kinds' workspace in
+ *                         p2s_interpolate_gaps: the columns go through it in chunks that fit, one column at least
  *   P2S_TUNE_DIAG_MODE    kernel diagnostics of a -DP2S_DIAG build (exp/README.md); refused by the shipped library */
 #define P2S_TUNE_TRI_PATH 1
 #define P2S_TUNE_FORCE_TILED 2
@@ -621,6 +623,7 @@ int p2s_get_assoc_stats(p2s_ctx *ctx, uint64_t *out, int32_t reset);
 #define P2S_TUNE_DEEP_PRUNE 10
 #define P2S_TUNE_SCREEN 11
 #define P2S_TUNE_POOL_TILES 12
+#define P2S_TUNE_GAPS_WORKSPACE_KB 13
 #define P2S_ASSOC_FORM_AUTO 0
 #define P2S_ASSOC_FORM_GENERAL 1
 #define P2S_TRI_PATH_AUTO 0
@@ -796,6 +799,47 @@ int p2s_assoc_unique_rows(int64_t n_frames, int32_t n_cams, int32_t n_max, const
                           int32_t n_threads, int32_t *uniq, int64_t *counts, int32_t *n_uniq);
 int p2s_assoc_filter_rows(int64_t n_frames, int32_t n_cams, int32_t n_max, const int32_t *uniq, const int32_t *n_uniq,
                           const int32_t *rank, int32_t min_cams, int32_t n_threads, int32_t *props, int32_t *n_props);
+
+/* ---- trajectory gaps after triangulation (csrc/p2s_gaps.hip) --------------------------------------
+ * The frame-sequential tail of triangulate_all (triangulation.py:888-953) for every column of a trial -- of all its
+ * persons side by side -- in one call each.  Host arrays in and out; ctx == NULL runs the same functions on the host.
+ * n_frames 1 .. 2^30, n_cols 1 .. 65535; a refused call (P2S_ERR_INVALID_ARG) has written nothing.
+ *
+ * p2s_interpolate_gaps: interpolate_zeros_nans (common.py:669-712) on coords [n_frames][n_cols] with the abscissae
+ * labels [n_frames] (strictly increasing, within +-2^53).  A sample is bad when it is NaN or == 0 (-0.0 included; +-inf
+ * is good).  A column with 4 or fewer good samples comes back untouched.  Bad samples form runs that break where two
+ * consecutive bad labels differ by more than 1; a run of more than max_gap samples (a count, or +inf) becomes NaN, the
+ * others take scipy's interp1d through the good samples:
+ *   P2S_GAPS_KIND_NONE       kind='linear' without extrapolation (np.interp's arithmetic, bit for bit; NaN beyond the
+ *                            first and last good label) -- the reference's call without a kind
+ *   P2S_GAPS_KIND_LINEAR     'linear', fill_value='extrapolate' (interp1d._call_linear, bit for bit)
+ *   P2S_GAPS_KIND_SLINEAR, _QUADRATIC, _CUBIC   make_interp_spline of degree 1, 2, 3 with scipy's knots, extrapolated;
+ *                            the banded system is solved without pivoting: scipy's values to rounding
+ * out [n_frames][n_cols]; status [n_cols]: 0, or P2S_GAPS_NONFINITE for a column of a spline kind with +-inf among its
+ * good samples, which comes back untouched (the caller's host path decides). */
+#define P2S_GAPS_KIND_NONE 0
+#define P2S_GAPS_KIND_LINEAR 1
+#define P2S_GAPS_KIND_SLINEAR 2
+#define P2S_GAPS_KIND_QUADRATIC 3
+#define P2S_GAPS_KIND_CUBIC 4
+#define P2S_GAPS_NONFINITE 1
+#define P2S_GAPS_WORKSPACE_KB (256 * 1024)
+int p2s_interpolate_gaps(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const double *coords, const int64_t *labels, double max_gap,
+                         int32_t kind, double *out, int32_t *status);
+/* fill_large_gaps_with (triangulation.py:922-926).  P2S_GAPS_FILL_LAST_VALUE: every NaN takes the last value before it
+ * that is not NaN, leading ones the first after them; what is still NaN (a column never seen) and +inf become 0.
+ * P2S_GAPS_FILL_ZEROS: NaN and +inf become 0.  Any other `how`: out = coords. */
+#define P2S_GAPS_FILL_LAST_VALUE 1
+#define P2S_GAPS_FILL_ZEROS 2
+int p2s_fill_gaps(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const double *coords, int32_t how, double *out);
+/* The spans of the report (triangulation.py:917-919, 946-953): per column of x [n_frames][n_cols] the runs of
+ * consecutive positions p, first < p < last, whose value is 0 or not finite.  table [capacity][4] gets the rows
+ * (column, start, end, long) -- long: more than max_gap positions -- by column, then by position; *count the rows there
+ * are.  With count > capacity the first `capacity` rows are written and *overflow is 1, else 0. */
+int p2s_gap_runs(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const double *x, int64_t first, int64_t last, double max_gap,
+                 int64_t capacity, int32_t *table, int64_t *count, int32_t *overflow);
+/* Kernel time of the last of the three calls above on this context, from HIP events around its kernels. */
+int p2s_gaps_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,9 @@ P2S_TRACK_MAX_SLOTS = 32   # person slots of p2s_track_persons_*: the rows of it
 P2S_TRACK_TILE = 32      # frames per tile of the map scan in csrc/p2s_extract.hip (T): tests place their cases around it
 (P2S_JSON_PERSON_ALL_INTS, P2S_JSON_PERSON_HAS_NULL, P2S_JSON_PERSON_HAS_BOOL, P2S_JSON_PERSON_BIG_INT, P2S_JSON_PERSON_NOT_OBJECT,
  P2S_JSON_PERSON_BAD_LIST) = 1, 2, 4, 8, 16, 32
+P2S_GAPS_KINDS = {None: 0, 'linear': 1, 'slinear': 2, 'quadratic': 3, 'cubic': 4}      # P2S_GAPS_KIND_*
+P2S_GAPS_FILLS = {'last_value': 1, 'zeros': 2}                                            # P2S_GAPS_FILL_*; anything else: 0
+P2S_GAPS_NONFINITE = 1
 P2S_MEASURE_SPEED, P2S_MEASURE_ANGLES, P2S_MEASURE_RESTRICT, P2S_MEASURE_FEET_CONST, P2S_MEASURE_HEIGHT, P2S_MEASURE_LEG = 1, 2, 4, 8, 16, 32
 P2S_MEASURE_ALL_SLOW, P2S_MEASURE_FEW_SMALL_ANGLES, P2S_MEASURE_ALL_DATA = 1, 2, 4
 P2S_MEASURE_ROLES = ('RShoulder', 'LShoulder', 'RHip', 'LHip', 'Hip', 'Neck', 'RKnee', 'LKnee', 'RAnkle', 'LAnkle')
@@ -120,6 +123,11 @@ SIGNATURES = {
     'p2s_track_persons_device': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                           C.c_double] + [C.c_void_p] * 9),
     'p2s_track_persons_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    'p2s_interpolate_gaps': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]),
+    'p2s_fill_gaps': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    'p2s_gap_runs': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_void_p,
+                               C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    'p2s_gaps_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     'p2s_json_person_flags': (C.c_int, [C.c_void_p, C.c_void_p]),
     'p2s_write_person_files': (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     'p2s_find_peaks_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]
@@ -166,7 +174,8 @@ OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_h
             'p2s_find_peaks_host', 'p2s_gait_contacts_host', 'p2s_gait_kernel_ms', 'p2s_stable_argsort_host',
             'p2s_trimmed_means_host', 'p2s_body_measure_host', 'p2s_measure_kernel_ms', 'p2s_track_select_host',
             'p2s_track_select_kernel_ms', 'p2s_json_person_flags', 'p2s_write_person_files', 'p2s_track_persons_host',
-            'p2s_track_persons_device', 'p2s_track_persons_kernel_ms'}
+            'p2s_track_persons_device', 'p2s_track_persons_kernel_ms', 'p2s_interpolate_gaps', 'p2s_fill_gaps', 'p2s_gap_runs',
+            'p2s_gaps_kernel_ms'}
 
 _lib = None
 

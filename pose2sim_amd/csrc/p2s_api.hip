@@ -271,6 +271,10 @@ int p2s_set_tuning(p2s_ctx *ctx, int32_t key, int32_t value) {
         if (value < 2 || value > 6) return p2s_set_error(P2S_ERR_INVALID_ARG, "tiles per wave outside [2, 6]");
         ctx->pool_tiles = value;
         return P2S_OK;
+    case P2S_TUNE_GAPS_WORKSPACE_KB:
+        if (value < 1) return p2s_set_error(P2S_ERR_INVALID_ARG, "workspace cap must be >= 1 KiB");
+        ctx->gaps_ws_kb = value;
+        return P2S_OK;
     case P2S_TUNE_ASSOC_FORM:
         if (value != P2S_ASSOC_FORM_AUTO && value != P2S_ASSOC_FORM_GENERAL)
             return p2s_set_error(P2S_ERR_INVALID_ARG, "unknown association kernel form %d", value);

@@ -192,6 +192,60 @@ def track_persons_3d_host(Q, first_frame=0, max_dist=None, state=None):
     return _track_persons(_lib.load(), None, Q, first_frame, max_dist, state)
 
 
+def _interpolate_gaps(lib, handle, coords, labels, max_gap, kind):
+    """p2s_interpolate_gaps on `handle` (None: the library's host path); what Engine.interpolate_gaps returns."""
+    fn = _entry(lib, 'p2s_interpolate_gaps')
+    coords = _matrix(coords)
+    labels = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
+    if len(labels) != len(coords):
+        raise P2sError(f'{len(labels)} labels for {len(coords)} frames')
+    out, status = np.empty_like(coords), np.zeros(coords.shape[1], dtype=np.int32)
+    code = _lib.P2S_GAPS_KINDS.get(kind, -1) if kind is None or isinstance(kind, str) else -1
+    _lib.check(fn(handle, coords.shape[0], coords.shape[1], _optr(coords), _optr(labels), float(max_gap), code, _optr(out), _optr(status)))
+    return out, status
+
+
+def _fill_gaps(lib, handle, coords, how):
+    fn = _entry(lib, 'p2s_fill_gaps')
+    coords = _matrix(coords)
+    out = np.empty_like(coords)
+    code = _lib.P2S_GAPS_FILLS.get(how, 0) if isinstance(how, str) else 0
+    _lib.check(fn(handle, coords.shape[0], coords.shape[1], _optr(coords), code, _optr(out)))
+    return out
+
+
+def _gap_runs(lib, handle, x, first, last, max_gap, capacity, raw):
+    fn = _entry(lib, 'p2s_gap_runs')
+    x = _matrix(x)
+    F, K = x.shape
+    cap = K * ((F + 1) // 2) if capacity is None else int(capacity)      # a run and the sample that ends it: no column holds more
+    table = np.empty((max(cap, 0), 4), dtype=np.int32)
+    count, over = C.c_int64(0), C.c_int32(0)
+    _lib.check(fn(handle, F, K, _optr(x), int(first), int(last), float(max_gap), cap, _ptr(table), C.byref(count), C.byref(over)))
+    table = table[:min(count.value, cap)]
+    if raw:
+        return table, count.value, bool(over.value)
+    if over.value:
+        raise P2sError(f'{count.value} runs do not fit a table of {cap}')
+    done, left = [[] for _ in range(K)], [[] for _ in range(K)]
+    for c, a, b, is_long in table.tolist():
+        (left if is_long else done)[c].append(f'{a}:{b}')
+    return done, left
+
+
+def interpolate_gaps_host(coords, labels, max_gap, kind):
+    """Engine.interpolate_gaps by the library's host path (no context, no GPU): the same code, for checking it."""
+    return _interpolate_gaps(_lib.load(), None, coords, labels, max_gap, kind)
+
+
+def fill_gaps_host(coords, how):
+    return _fill_gaps(_lib.load(), None, coords, how)
+
+
+def gap_runs_host(x, first, last, max_gap, capacity=None, raw=False):
+    return _gap_runs(_lib.load(), None, x, first, last, max_gap, capacity, raw)
+
+
 class Engine:
     def __init__(self, device=0):
         self._lib = _lib.load()
@@ -237,7 +291,7 @@ class Engine:
 
     # p2s_set_tuning keys (include/p2s.h): experiments and tests only, results never depend on them
     TUNE_TRI_PATH, TUNE_FORCE_TILED, TUNE_NO_OVERLAP, TUNE_SEARCH_JOB, TUNE_DIAG_MODE, TUNE_MAX_SUBSETS, TUNE_DEEP_MIN_SUBSETS = 1, 2, 3, 4, 5, 6, 7
-    TUNE_ASSOC_FORM, TUNE_POOL_SINGLES_PCT, TUNE_DEEP_PRUNE, TUNE_SCREEN, TUNE_POOL_TILES = 8, 9, 10, 11, 12
+    TUNE_ASSOC_FORM, TUNE_POOL_SINGLES_PCT, TUNE_DEEP_PRUNE, TUNE_SCREEN, TUNE_POOL_TILES, TUNE_GAPS_WORKSPACE_KB = 8, 9, 10, 11, 12, 13
     TRI_PATH_AUTO, TRI_PATH_WORKLIST, TRI_PATH_ONE_TILE, TRI_PATH_POOLED, TRI_PATH_TWO_TILES = 0, 1, 2, 3, 4
     ASSOC_FORM_AUTO, ASSOC_FORM_GENERAL = 0, 1
 
@@ -845,6 +899,31 @@ class Engine:
     def track_persons_kernel_ms(self):
         """Kernel time of the last track_persons_3d() call, from HIP events around its kernel."""
         return _kernel_ms(self, 'track_persons')
+
+    # -- trajectory gaps after triangulation (triangulation.py:888-953) -------------------------------------------------------
+    def interpolate_gaps(self, coords, labels, max_gap, kind):
+        """postproc.interpolate_gaps for coords [F][C] float64 -- all persons of a trial as columns side by side -- with the
+        frame numbers labels [F] (increasing): bad samples (NaN or 0) in runs of at most max_gap (a count or inf) take
+        interp1d's value through the column's good samples, longer runs become NaN, columns with 4 or fewer good samples stay.
+        kind: None (linear, no extrapolation), 'linear', 'slinear', 'quadratic', 'cubic' (csrc/p2s_gaps.hip).
+        -> (out [F][C], status [C] int32: nonzero for a column the kernels left untouched -- a spline kind with +-inf among
+        its good samples).  The input is not modified."""
+        return _interpolate_gaps(self._lib, self._h, coords, labels, max_gap, kind)
+
+    def fill_gaps(self, coords, how):
+        """postproc.fill_gaps on a copy: 'last_value', 'zeros'; anything else returns the table as it is."""
+        return _fill_gaps(self._lib, self._h, coords, how)
+
+    def gap_runs(self, x, first, last, max_gap, capacity=None, raw=False):
+        """postproc.gap_spans for x [F][K]: (done, left), per column the 'a:b' runs of positions strictly between first and
+        last that are 0 or not finite -- those of at most max_gap positions, and the longer ones.  capacity: rows of the
+        device table (default: what F frames can hold at most); raw=True -> (table [n][4] int32 of (column, start, end,
+        long), count, overflow) instead, without raising when the table was too small."""
+        return _gap_runs(self._lib, self._h, x, first, last, max_gap, capacity, raw)
+
+    def gaps_kernel_ms(self):
+        """Kernel time of the last interpolate_gaps(), fill_gaps() or gap_runs() call, from HIP events around its kernels."""
+        return _kernel_ms(self, 'gaps')
 
     # -- synchronization (synchronization.py:1271-1343, 1541-1585) -------------------------------------------------------
     def sync_speeds(self, coords, b, a, zi):

@@ -1,6 +1,9 @@
 """Sequential host steps after the kernel: person tracking across frames, gap interpolation,
 valid-section selection, gap filling.  They run on the gathered result on rank 0 (SURVEY.md
-section 8e: these steps carry state from frame to frame and do not shard).
+section 8e: these steps carry state from frame to frame and do not shard).  Tracking, gap
+interpolation, the interpolated spans and gap filling also exist as kernels (csrc/p2s_track.hip,
+csrc/p2s_gaps.hip); the functions here are what the stage runs without them and what they are
+checked against.
 """
 import numpy as np
 from scipy import interpolate

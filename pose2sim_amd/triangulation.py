@@ -2,10 +2,10 @@
 (triangulation.py:656-959), with the per-(frame x person x keypoint) work on the MI355X.
 
 The frame / person / keypoint loops (triangulation.py:796-845) become ONE call into the HIP
-engine over the packed tensor of every frame, and person tracking across the frames (:847-865)
-one more; what stays on the host is the rest of the frame-sequential tail: interpolation
-(:889-894), valid-section trimming (:897-919), gap filling (:922-926), the .trc writer (:929)
-and the recap log (:959).
+engine over the packed tensor of every frame, person tracking across the frames (:847-865)
+one more, and gap interpolation (:889-894), the interpolated spans (:917-919) and gap filling
+(:922-926) one each; what stays on the host is the choice of the kept section (:897-910), the
+.trc writer (:929) and the recap log (:959).
 There is no CPU fallback for the kernel work.
 """
 import logging
@@ -132,6 +132,13 @@ def finish_person(n, coords, err_frame, excl_frame, frames, settings, config_dic
             coords = postproc.interpolate_gaps(coords, frames, settings['max_gap'], settings['interpolation'])
         except Exception:
             logging.warning(f'Interpolation was not possible for person {n}. This means that not enough points are available, which is often due to a bad calibration.')
+    return _finish_interpolated(n, coords, err_frame, excl_frame, frames, settings, config_dict, keypoints_names, write,
+                                postproc.gap_spans, postproc.fill_gaps)
+
+
+def _finish_interpolated(n, coords, err_frame, excl_frame, frames, settings, config_dict, keypoints_names, write, gap_spans, fill_gaps):
+    """finish_person from the kept section on (triangulation.py:897-953); gap_spans and fill_gaps are postproc's or the
+    engine's."""
     start, end = postproc.indices_of_first_last_non_nan_chunks(err_frame, min_chunk_size=settings['min_chunk_size'],
                                                                chunk_choice_method=settings['sections_to_keep'])
     person = PersonTrial(start, end)
@@ -140,8 +147,8 @@ def finish_person(n, coords, err_frame, excl_frame, frames, settings, config_dic
         return person
     person.kept = True
     coords = coords[start:end]
-    done, left = postproc.gap_spans(coords[:, ::3], start, end, settings['max_gap'])             # before the long gaps are filled
-    coords = postproc.fill_gaps(coords, settings['fill_large_gaps_with'])
+    done, left = gap_spans(coords[:, ::3], start, end, settings['max_gap'])                      # before the long gaps are filled
+    coords = fill_gaps(coords, settings['fill_large_gaps_with'])
     if write:
         seq_name = os.path.basename(os.path.realpath(config_dict.get('project').get('project_dir')))
         if config_dict.get('project').get('multi_person'):
@@ -157,6 +164,49 @@ def finish_person(n, coords, err_frame, excl_frame, frames, settings, config_dic
     else:
         person.interpolated, person.not_interpolated = None, []
     return person
+
+
+GAP_KINDS_ENGINE = ('linear', 'slinear', 'quadratic', 'cubic')   # with None, the kinds csrc/p2s_gaps.hip restates
+# Trials shorter than this stay on the host.  Measured: at 100 frames x 78 columns the device path takes
+# 0.48 ms against the host's 2.02 ms ('linear'; 'cubic' 0.61 against 3.61 ms) and it wins at every length up to 100 000: no
+# crossover, so no trial is too short.
+GAPS_MIN_FRAMES_ENGINE = 0
+
+
+def finish_persons_engine(engine, coords, err_frames, excl_frames, frames, settings, config_dict, keypoints_names, write):
+    """finish_person for every person of a trial with the gap steps on the GPU (csrc/p2s_gaps.hip): coords, one [F][3 K]
+    table a person; err_frames / excl_frames [F][P].  One Engine.interpolate_gaps call takes all persons as columns side
+    by side; then per person the kept section (host: an F-vector), Engine.gap_runs, Engine.fill_gaps and the .trc file.
+    The same files, PersonTrial fields and log lines as finish_person person after person.  The host functions take
+    over, silently, when the engine lacks the calls (a library built before them, a test double), when the kind is not
+    one the kernels restate, and -- for that person, whole -- when one of a person's columns comes back with a status:
+    the reference interpolates all of a person's columns or none."""
+    kind, n_persons = settings['interpolation'], len(coords)
+
+    def host(n):
+        return finish_person(n, coords[n], err_frames[:, n], excl_frames[:, n], frames, settings, config_dict, keypoints_names, write)
+
+    calls = [getattr(engine, name, None) for name in ('interpolate_gaps', 'gap_runs', 'fill_gaps')]
+    if None in calls or not n_persons or len(frames) < max(GAPS_MIN_FRAMES_ENGINE, 1) or not (kind == 'none' or kind in GAP_KINDS_ENGINE):
+        return [host(n) for n in range(n_persons)]
+    interpolate, gap_runs, fill_gaps = calls
+    widths = np.cumsum([0] + [c.shape[1] for c in coords])
+    try:
+        if kind == 'none':
+            tables, status = coords, np.zeros(widths[-1], dtype=np.int32)
+        else:
+            out, status = interpolate(np.concatenate(coords, axis=1), frames, settings['max_gap'], kind)
+            tables = [out[:, widths[n]:widths[n + 1]] for n in range(n_persons)]
+        people = []
+        for n in range(n_persons):
+            if np.any(status[widths[n]:widths[n + 1]]):
+                people.append(host(n))
+            else:
+                people.append(_finish_interpolated(n, tables[n], err_frames[:, n], excl_frames[:, n], frames, settings, config_dict,
+                                                   keypoints_names, write, gap_runs, fill_gaps))
+        return people
+    except NotImplementedError:
+        return [host(n) for n in range(n_persons)]
 
 
 def table_figures(person, err, n_excl, masks, n_cams):
@@ -270,8 +320,8 @@ def triangulate_all(config_dict):
         Q_rows, ids = track_persons_engine(engine, Qk, f_range, multi_person, max_distance_m)
         e_fr = in_tracked_order(err_frames, ids, np.nan)
         x_fr = in_tracked_order(excl_frames, ids, float(n_cams))
-        people = [finish_person(n, Q_rows[:, n].reshape(len(frames), keypoints_nb * 3), e_fr[:, n], x_fr[:, n], frames, settings,
-                                config_dict, keypoints_names, write=(rank == 0)) for n in range(nb_persons)]
+        people = finish_persons_engine(engine, [Q_rows[:, n].reshape(len(frames), keypoints_nb * 3) for n in range(nb_persons)], e_fr, x_fr,
+                                       frames, settings, config_dict, keypoints_names, write=(rank == 0))
         if all(p.end == p.start for p in people):                              # :955-956
             raise Exception('No persons have been triangulated. Please check your calibration and your synchronization, or the triangulation parameters in Config.toml.')
         return people, ids
