@@ -841,6 +841,34 @@ int p2s_gap_runs(p2s_ctx *ctx, int64_t n_frames, int32_t n_cols, const double *x
 /* Kernel time of the last of the three calls above on this context, from HIP events around its kernels. */
 int p2s_gaps_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
 
+/* ---- confidence timeline (Utilities/confidence_timeline.py:89-130; csrc/p2s_timeline.hip) ------------
+ * The rows of the reference's CSV and the series of its plot for every camera folder in one call.  Host arrays in and
+ * out; ctx == NULL runs the same functions on the host.  Camera c has the files file_off[c] .. file_off[c + 1]
+ * (file_off[0] = 0, a camera may have none); file f lists the persons person_base[f] .. person_base[f + 1] of valid [N]
+ * (nonzero: the list held at least 78 numbers) and conf [N][n_kpts] (the confidences of the 1 .. 26 resolved keypoints).
+ * Rows: a file contributes n_kpts rows for every valid person, by frame (the file's position in its camera), then
+ * person (the position in the file's list, invalid entries counted), then slot (the index into the resolved names):
+ *   row_off [n_cams + 1]; frame, person, slot (int32) and confidence [n_rows], n_rows = n_kpts x the valid persons.
+ * Series: n_people [n_cams] is the longest list of every camera, P_c.  For every camera and every person index below
+ * P_c, in that order, one series: the files in which that entry is valid, in file order:
+ *   series_off [n_series + 1], n_series = the sum of P_c; series_frame [n_rows / n_kpts]; series_conf
+ *   [n_kpts][n_rows / n_kpts], slot-major, a series at the same offsets in every slot.
+ * n_rows and n_series are the caller's sizes of these arrays: other values than the input's are refused
+ * (P2S_ERR_INVALID_ARG, nothing written, the message names the right ones).  Fewer than 2^31 files and persons. */
+int p2s_timeline_rows_host(p2s_ctx *ctx, int32_t n_cams, const int64_t *file_off, const int64_t *person_base, const uint8_t *valid,
+                           int32_t n_kpts, const double *conf, int64_t n_rows, int64_t n_series, int64_t *row_off, int32_t *frame,
+                           int32_t *person, int32_t *slot, double *confidence, int64_t *n_people, int64_t *series_off,
+                           int32_t *series_frame, double *series_conf);
+/* Milliseconds the kernels of this context's last p2s_timeline_rows_host took (HIP events around them). */
+int p2s_timeline_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
+/* The reference's confidence_timeline.csv (csv.writer, newline=''): the header frame,person,keypoint,confidence and one
+ * line a row, terminated by \r\n, the keypoint as names[name_off[slot] .. name_off[slot + 1]], the confidence as
+ * repr(float): shortest digits that round-trip, nan, inf, -inf.  Row ranges are formatted on host threads (n_threads, 0
+ * = the machine's, at most 32) and written in order.  The file is created or truncated.  A name holding a comma, a quote
+ * or a line break, or a slot outside the names, is refused before the file is opened. */
+int p2s_timeline_write_csv(const char *path, int64_t n_rows, const int32_t *frame, const int32_t *person, const int32_t *slot,
+                           const double *confidence, int32_t n_names, const char *names, const int64_t *name_off, int32_t n_threads);
+
 #ifdef __cplusplus
 }
 #endif

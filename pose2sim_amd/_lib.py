@@ -128,6 +128,10 @@ SIGNATURES = {
     'p2s_gap_runs': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_void_p,
                                C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     'p2s_gaps_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    'p2s_timeline_rows_host': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                        C.c_int64] + [C.c_void_p] * 9),
+    'p2s_timeline_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    'p2s_timeline_write_csv': (C.c_int, [C.c_char_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int32, C.c_char_p, C.c_void_p, C.c_int32]),
     'p2s_json_person_flags': (C.c_int, [C.c_void_p, C.c_void_p]),
     'p2s_write_person_files': (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     'p2s_find_peaks_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]
@@ -175,7 +179,7 @@ OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_h
             'p2s_trimmed_means_host', 'p2s_body_measure_host', 'p2s_measure_kernel_ms', 'p2s_track_select_host',
             'p2s_track_select_kernel_ms', 'p2s_json_person_flags', 'p2s_write_person_files', 'p2s_track_persons_host',
             'p2s_track_persons_device', 'p2s_track_persons_kernel_ms', 'p2s_interpolate_gaps', 'p2s_fill_gaps', 'p2s_gap_runs',
-            'p2s_gaps_kernel_ms'}
+            'p2s_gaps_kernel_ms', 'p2s_timeline_rows_host', 'p2s_timeline_kernel_ms', 'p2s_timeline_write_csv'}
 
 _lib = None
 

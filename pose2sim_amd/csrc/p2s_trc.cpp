@@ -3,6 +3,8 @@
 // `frame \t time \t v1 \t v2 ...`, floats as Python's repr() prints them (shortest digits that round-trip, fixed
 // notation for 1e-4 <= |v| < 1e16, otherwise d.ddde+XX), NaN as an empty field.  pandas formats every value
 // through a Python object; at 100 k frames x 78 columns that is ~20 s, this writer takes a fraction of a second.
+// Also the rows of Utilities/confidence_timeline.py's CSV (p2s_timeline_write_csv): csv.writer's text, NaN as 'nan'.
+#include <algorithm>
 #include <cerrno>
 #include <charconv>
 #include <cmath>
@@ -139,6 +141,68 @@ int p2s_trc_append_rows(const char *path, int64_t n_rows, int32_t n_cols, const 
                     *o++ = '\n';
                 }
                 used[(size_t)slot] = (size_t)(o - b.data());
+            });
+            if (!done) throw std::bad_alloc();
+            for (int t = 0; t < n_blocks; ++t)
+                if (fwrite(bufs[(size_t)t].data(), 1, used[(size_t)t], fh) != used[(size_t)t])
+                    rc = p2s_set_error(P2S_ERR_INVALID_ARG, "short write to %s", path);
+        }
+    } catch (const std::bad_alloc &) {
+        rc = p2s_set_error(P2S_ERR_OOM, "out of host memory while formatting");
+    }
+    if (fclose(fh) != 0 && rc == P2S_OK) rc = p2s_set_error(P2S_ERR_INVALID_ARG, "error closing %s", path);
+    return rc;
+}
+
+int p2s_timeline_write_csv(const char *path, int64_t n_rows, const int32_t *frame, const int32_t *person, const int32_t *slot,
+                           const double *confidence, int32_t n_names, const char *names, const int64_t *name_off, int32_t n_threads) {
+    if (!path || n_rows < 0 || n_names < 0 || (n_names > 0 && (!names || !name_off)) || (n_rows > 0 && (!frame || !person || !slot || !confidence)))
+        return p2s_set_error(P2S_ERR_INVALID_ARG, "bad arguments");
+    size_t longest = 0;
+    for (int32_t k = 0; k < n_names; ++k) {
+        if (name_off[k + 1] < name_off[k]) return p2s_set_error(P2S_ERR_INVALID_ARG, "name_off must not decrease");
+        longest = std::max(longest, (size_t)(name_off[k + 1] - name_off[k]));
+        for (int64_t i = name_off[k]; i < name_off[k + 1]; ++i)
+            if (names[i] == ',' || names[i] == '"' || names[i] == '\r' || names[i] == '\n')
+                return p2s_set_error(P2S_ERR_INVALID_ARG, "name %d holds a character csv.writer would quote", k);
+    }
+    for (int64_t r = 0; r < n_rows; ++r)
+        if (slot[r] < 0 || slot[r] >= n_names) return p2s_set_error(P2S_ERR_INVALID_ARG, "row %lld names slot %d of %d", (long long)r, slot[r], n_names);
+    FILE *fh = fopen(path, "wb");
+    if (!fh) return p2s_set_error(P2S_ERR_INVALID_ARG, "cannot open %s for writing", path);
+    static const char head[] = "frame,person,keypoint,confidence\r\n";
+    int rc = fwrite(head, 1, sizeof head - 1, fh) == sizeof head - 1 ? P2S_OK : p2s_set_error(P2S_ERR_INVALID_ARG, "short write to %s", path);
+    const int nt = host_threads(n_threads, 32, 32);
+    const int64_t block = 16384;                              // rows formatted per task
+    const size_t row_cap = 11 + 1 + 11 + 1 + longest + 1 + 25 + 2;
+    try {
+        // as p2s_trc_append_rows: a group of nt blocks is formatted in parallel and written in order
+        std::vector<std::vector<char>> bufs((size_t)nt);
+        std::vector<size_t> used((size_t)nt);
+        for (int64_t g0 = 0; g0 < n_rows && rc == P2S_OK; g0 += block * nt) {
+            const int64_t left = (n_rows - g0 + block - 1) / block;
+            const int n_blocks = (int)(left < nt ? left : nt);
+            const bool done = parallel_for(n_blocks, n_blocks, 1, [&](int, int64_t b, int64_t) {
+                const int64_t lo = g0 + b * block;
+                const int64_t hi = lo + block < n_rows ? lo + block : n_rows;
+                std::vector<char> &buf = bufs[(size_t)b];
+                buf.resize((size_t)(hi - lo) * row_cap);
+                char *o = buf.data();
+                for (int64_t r = lo; r < hi; ++r) {
+                    o = put_int(o, frame[r]);
+                    *o++ = ',';
+                    o = put_int(o, person[r]);
+                    *o++ = ',';
+                    const size_t len = (size_t)(name_off[slot[r] + 1] - name_off[slot[r]]);
+                    memcpy(o, names + name_off[slot[r]], len);
+                    o += len;
+                    *o++ = ',';
+                    if (confidence[r] != confidence[r]) { memcpy(o, "nan", 3); o += 3; }      // repr(float('nan')), whatever its sign
+                    else o = py_repr(o, confidence[r]);
+                    *o++ = '\r';
+                    *o++ = '\n';
+                }
+                used[(size_t)b] = (size_t)(o - buf.data());
             });
             if (!done) throw std::bad_alloc();
             for (int t = 0; t < n_blocks; ++t)

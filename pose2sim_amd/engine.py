@@ -246,6 +246,59 @@ def gap_runs_host(x, first, last, max_gap, capacity=None, raw=False):
     return _gap_runs(_lib.load(), None, x, first, last, max_gap, capacity, raw)
 
 
+TIMELINE_MAX_KPTS = 26
+
+
+def _timeline_rows(lib, handle, file_off, person_base, valid, conf):
+    """p2s_timeline_rows_host on `handle` (None: the library's host path); what Engine.timeline_rows returns."""
+    fn = _entry(lib, 'p2s_timeline_rows_host')
+    file_off = np.ascontiguousarray(file_off, dtype=np.int64).reshape(-1)
+    person_base = np.ascontiguousarray(person_base, dtype=np.int64).reshape(-1)
+    valid = np.ascontiguousarray(np.asarray(valid).reshape(-1) != 0, dtype=np.uint8)
+    conf = np.ascontiguousarray(conf, dtype=np.float64)
+    if len(file_off) < 2 or file_off[0] != 0 or (np.diff(file_off) < 0).any():
+        raise ValueError('file_off must rise from 0, one entry a camera and one more')
+    if len(person_base) != file_off[-1] + 1 or person_base[0] != 0 or (np.diff(person_base) < 0).any():
+        raise ValueError(f'person_base must rise from 0 and have {int(file_off[-1]) + 1} entries, one a file and one more')
+    N = int(person_base[-1])
+    if len(valid) != N or conf.ndim != 2 or len(conf) != N:
+        raise ValueError(f'valid [{N}] and conf [{N}][K] are required: one entry a listed person')
+    K = conf.shape[1]
+    if not 1 <= K <= TIMELINE_MAX_KPTS:
+        raise ValueError(f'conf has {K} keypoints; expected 1 .. {TIMELINE_MAX_KPTS}')
+    Cn, nv = len(file_off) - 1, int(valid.sum())
+    counts = np.diff(person_base)
+    S = sum(int(counts[a:b].max(initial=0)) for a, b in zip(file_off[:-1], file_off[1:]))
+    out = {'row_off': np.zeros(Cn + 1, dtype=np.int64), 'frame': np.empty(K * nv, dtype=np.int32), 'person': np.empty(K * nv, dtype=np.int32),
+           'slot': np.empty(K * nv, dtype=np.int32), 'confidence': np.empty(K * nv), 'n_people': np.zeros(Cn, dtype=np.int64),
+           'series_off': np.zeros(S + 1, dtype=np.int64), 'series_frame': np.empty(nv, dtype=np.int32), 'series_conf': np.empty((K, nv))}
+    _lib.check(fn(handle, Cn, _ptr(file_off), _ptr(person_base), _optr(valid), K, _optr(conf), K * nv, S, _ptr(out['row_off']),
+                  _optr(out['frame']), _optr(out['person']), _optr(out['slot']), _optr(out['confidence']), _ptr(out['n_people']),
+                  _ptr(out['series_off']), _optr(out['series_frame']), _optr(out['series_conf'])))
+    return out
+
+
+def timeline_rows_host(file_off, person_base, valid, conf):
+    """Engine.timeline_rows by the library's host path (no context, no GPU): the same code, for checking it."""
+    return _timeline_rows(_lib.load(), None, file_off, person_base, valid, conf)
+
+
+def write_timeline_csv(path, frame, person, slot, confidence, names, n_threads=0):
+    """The reference's confidence_timeline.csv (csv.writer with newline='') by the native writer on host threads
+    (p2s_timeline_write_csv): header, then `frame,person,names[slot],repr(confidence)` and \\r\\n for every row."""
+    import os
+    lib = _lib.load()
+    fn = _entry(lib, 'p2s_timeline_write_csv')
+    frame, person, slot = (np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (frame, person, slot))
+    confidence = np.ascontiguousarray(confidence, dtype=np.float64).reshape(-1)
+    if not len(frame) == len(person) == len(slot) == len(confidence):
+        raise ValueError('frame, person, slot and confidence must have one entry a row')
+    enc = [n.encode() for n in names]
+    off = _offsets([len(e) for e in enc])
+    _lib.check(fn(os.fsencode(path), len(frame), _optr(frame), _optr(person), _optr(slot), _optr(confidence), len(enc), b''.join(enc),
+                  _ptr(off), int(n_threads)))
+
+
 class Engine:
     def __init__(self, device=0):
         self._lib = _lib.load()
@@ -924,6 +977,22 @@ class Engine:
     def gaps_kernel_ms(self):
         """Kernel time of the last interpolate_gaps(), fill_gaps() or gap_runs() call, from HIP events around its kernels."""
         return _kernel_ms(self, 'gaps')
+
+    # -- confidence timeline (Utilities/confidence_timeline.py:89-130) ---------------------------------------------------------
+    def timeline_rows(self, file_off, person_base, valid, conf):
+        """The rows and series of confidence_timeline for every camera folder in one call (csrc/p2s_timeline.hip).
+        file_off [C + 1]: the files of every camera; person_base [n_files + 1]: the listed persons of every file; valid
+        [N]: the person's list held at least 78 numbers; conf [N][K] float64, 1 <= K <= 26: the confidences of the resolved
+        keypoints.  -> dict: 'row_off' [C + 1] int64 and, a row for every (file, valid person, slot) in that order,
+        'frame', 'person', 'slot' int32 (camera-local file, position in the file's list, index into the K keypoints) and
+        'confidence'; 'n_people' [C] the longest list of every camera; 'series_off' [sum(n_people) + 1] int64, one series
+        per camera and person index below n_people: 'series_frame' the files whose entry is valid, in order, and
+        'series_conf' [K][valid persons] their confidences, slot-major.  Bad offsets, lengths or K raise ValueError."""
+        return _timeline_rows(self._lib, self._h, file_off, person_base, valid, conf)
+
+    def timeline_kernel_ms(self):
+        """Kernel time of the last timeline_rows() call, from HIP events around its kernels."""
+        return _kernel_ms(self, 'timeline')
 
     # -- synchronization (synchronization.py:1271-1343, 1541-1585) -------------------------------------------------------
     def sync_speeds(self, coords, b, a, zi):
