@@ -869,6 +869,55 @@ int p2s_timeline_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
 int p2s_timeline_write_csv(const char *path, int64_t n_rows, const int32_t *frame, const int32_t *person, const int32_t *slot,
                            const double *confidence, int32_t n_names, const char *names, const int64_t *name_off, int32_t n_threads);
 
+/* ---- extrinsics refinement from keypoints (csrc/p2s_refine.hip) -------------------------------------
+ * Bundle adjustment of the cameras' rotations and translations on the 2D keypoints of a trial, the 3D points eliminated
+ * by the Schur complement; intrinsics are held and the observations are pinhole (undistorted) pixels.  Host arrays in and
+ * out, fp64 throughout; ctx == NULL runs the same functions on the host.
+ *   xyl [n_points][n_cams][3] (x px, y px, likelihood; dtype P2S_F32 / P2S_F64), Kmats [n_cams][9], R_in [n_cams][9]
+ *   (world -> camera, row-major), t_in [n_cams][3], X0 [n_points][3] the start points.
+ * Weight of an observation: s = l when l >= lik_thr and x, y, l are finite, else 0.  A point with fewer than min_cams
+ * (raised to 2) observations of s > 0, or with a non-finite X0 row, is dropped: its weights are 0 and its row of X_out is
+ * NaN.  Residuals e = s (u_proj - u_obs), s (v_proj - v_obs) with u_proj = fx Xc.x / Xc.z + cx, Xc = R X + t; the cost is
+ * the sum over the components of e^2 for |e| <= huber_px, else 2 huber_px |e| - huber_px^2 (scipy's loss='huber' with
+ * f_scale = huber_px, without its factor 1/2).  Gauge: camera 0 is held, and of camera 1's translation the coordinate
+ * j = argmax_j |(t1 - R1 R0^T t0)_j| (first index on ties): 6 n_cams - 7 free parameters.  Levenberg-Marquardt from
+ * lambda = 1e-3 (/ 10 on an accepted trial, floor 1e-9; x 10 on a refused one), one trial an iteration, until the
+ * relative decrease of an accepted trial is below ftol, a refused trial's cost is within ftol of the current one,
+ * max_iter trials have run, or lambda > 1e12.
+ * R_out, t_out [n_cams][..], X_out [n_points][3]; max_iter = 0 hands the input back with cost_after = cost_before.
+ * Refused with P2S_ERR_INVALID_ARG, before any refinement kernel runs: n_cams outside 2 .. P2S_MAX_CAMS, non-finite Kmats,
+ * R_in or t_in, no kept point, a camera without a kept observation, a kept observation whose point lies behind its
+ * camera (Xc.z <= 0) at entry; the message names the camera (and the point).  Two calls on the same input return the same
+ * bits: every sum is taken in a fixed order, P2S_REFINE_TILE points a workgroup pass, at most P2S_REFINE_MAX_PARTS
+ * partial sums of a launch. */
+#define P2S_REFINE_TILE 256
+#define P2S_REFINE_MAX_PARTS 128
+typedef struct p2s_refine_params {
+    double lik_thr;      /* observations below it do not count */
+    double huber_px;     /* delta of the Huber loss, px of weighted residual (> 0) */
+    double ftol;         /* relative decrease of the cost that ends the iteration */
+    int32_t min_cams;    /* cameras a point needs (values below 2 are taken as 2) */
+    int32_t max_iter;    /* Levenberg-Marquardt trials at most (>= 0) */
+} p2s_refine_params;
+typedef struct p2s_refine_report {
+    double cost_before, cost_after;   /* the Huber cost at the input and at the output */
+    double lambda_final;
+    int64_t kept_points;
+    int32_t iterations, accepted;     /* trials run; trials that lowered the cost */
+    int32_t held_coord;               /* j: the coordinate of camera 1's translation that is held */
+    int32_t reserved;
+    double rms_before[P2S_MAX_CAMS];  /* per camera sqrt(sum s^2 d^2 / sum s^2), d the reprojection distance in px */
+    double rms_after[P2S_MAX_CAMS];
+} p2s_refine_report;
+int p2s_refine_extrinsics_host(p2s_ctx *ctx, int64_t n_points, int32_t n_cams, int32_t dtype, const void *xyl, const double *Kmats,
+                               const double *R_in, const double *t_in, const double *X0, const p2s_refine_params *params,
+                               double *R_out, double *t_out, double *X_out, p2s_refine_report *report);
+/* Milliseconds between the HIP events around this context's last p2s_refine_extrinsics_host: its kernels and the
+ * reduced solves on the host between them. */
+int p2s_refine_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
+/* The held coordinate j of the gauge above from R_in and t_in of cameras 0 and 1 (host arithmetic, no context). */
+int p2s_refine_held_coord(const double *R_in, const double *t_in, int32_t *held);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,7 +37,8 @@ P2S_GAPS_FILLS = {'last_value': 1, 'zeros': 2}                                  
 P2S_GAPS_NONFINITE = 1
 P2S_MEASURE_SPEED, P2S_MEASURE_ANGLES, P2S_MEASURE_RESTRICT, P2S_MEASURE_FEET_CONST, P2S_MEASURE_HEIGHT, P2S_MEASURE_LEG = 1, 2, 4, 8, 16, 32
 P2S_MEASURE_ALL_SLOW, P2S_MEASURE_FEW_SMALL_ANGLES, P2S_MEASURE_ALL_DATA = 1, 2, 4
-P2S_MEASURE_ROLES = ('RShoulder', 'LShoulder', 'RHip', 'LHip', 'Hip', 'Neck', 'RKnee', 'LKnee', 'RAnkle', 'LAnkle')
+P2S_REFINE_TILE, P2S_REFINE_MAX_PARTS = 256, 128   # csrc/p2s_refine.hip: points a workgroup pass, partial sums a launch
+P2S_MEASURE_ROLES =('RShoulder', 'LShoulder', 'RHip', 'LHip', 'Hip', 'Neck', 'RKnee', 'LKnee', 'RAnkle', 'LAnkle')
 
 
 class TriParams(C.Structure):
@@ -64,6 +65,27 @@ class SingleParams(C.Structure):
                 ('likelihood_threshold', C.c_double),
                 ('min_cameras', C.c_int32),
                 ('reserved', C.c_int32)]
+
+
+class RefineParams(C.Structure):
+    _fields_ = [('lik_thr', C.c_double),
+                ('huber_px', C.c_double),
+                ('ftol', C.c_double),
+                ('min_cams', C.c_int32),
+                ('max_iter', C.c_int32)]
+
+
+class RefineReport(C.Structure):
+    _fields_ = [('cost_before', C.c_double),
+                ('cost_after', C.c_double),
+                ('lambda_final', C.c_double),
+                ('kept_points', C.c_int64),
+                ('iterations', C.c_int32),
+                ('accepted', C.c_int32),
+                ('held_coord', C.c_int32),
+                ('reserved', C.c_int32),
+                ('rms_before', C.c_double * P2S_MAX_CAMS),
+                ('rms_after', C.c_double * P2S_MAX_CAMS)]
 
 
 # name -> (restype, argtypes); every symbol include/p2s.h declares
@@ -132,6 +154,10 @@ SIGNATURES = {
                                         C.c_int64] + [C.c_void_p] * 9),
     'p2s_timeline_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     'p2s_timeline_write_csv': (C.c_int, [C.c_char_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int32, C.c_char_p, C.c_void_p, C.c_int32]),
+    'p2s_refine_extrinsics_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.POINTER(RefineParams)]
+                                   + [C.c_void_p] * 3 + [C.POINTER(RefineReport)]),
+    'p2s_refine_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    'p2s_refine_held_coord': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     'p2s_json_person_flags': (C.c_int, [C.c_void_p, C.c_void_p]),
     'p2s_write_person_files': (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     'p2s_find_peaks_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]
@@ -179,7 +205,8 @@ OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_h
             'p2s_trimmed_means_host', 'p2s_body_measure_host', 'p2s_measure_kernel_ms', 'p2s_track_select_host',
             'p2s_track_select_kernel_ms', 'p2s_json_person_flags', 'p2s_write_person_files', 'p2s_track_persons_host',
             'p2s_track_persons_device', 'p2s_track_persons_kernel_ms', 'p2s_interpolate_gaps', 'p2s_fill_gaps', 'p2s_gap_runs',
-            'p2s_gaps_kernel_ms', 'p2s_timeline_rows_host', 'p2s_timeline_kernel_ms', 'p2s_timeline_write_csv'}
+            'p2s_gaps_kernel_ms', 'p2s_timeline_rows_host', 'p2s_timeline_kernel_ms', 'p2s_timeline_write_csv',
+            'p2s_refine_extrinsics_host', 'p2s_refine_kernel_ms', 'p2s_refine_held_coord'}
 
 _lib = None
 

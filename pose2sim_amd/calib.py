@@ -83,8 +83,9 @@ def find_calibration_file(session_dir):
     return calib_file
 
 
-def write_calibration_toml(path, cams):
-    """Write a calibration in the schema of calibration.py:1504-1533 (used by tests / demos)."""
+def write_calibration_toml(path, cams, adjusted=False, error=0.0):
+    """Write a calibration in the schema of calibration.py:1504-1533 (used by tests / demos, and by calib_refine with
+    adjusted=True)."""
     with open(path, 'w') as f:
         for c in range(len(cams['K'])):
             name = cams['names'][c] if 'names' in cams else f'cam_{c + 1:02d}'
@@ -98,4 +99,4 @@ def write_calibration_toml(path, cams):
             f.write('rotation = [ ' + ', '.join(repr(float(v)) for v in np.asarray(cams['R'][c]).ravel()) + ']\n')
             f.write('translation = [ ' + ', '.join(repr(float(v)) for v in np.asarray(cams['T'][c]).ravel()) + ']\n')
             f.write('fisheye = false\n\n')
-        f.write('[metadata]\nadjusted = false\nerror = 0.0\n')
+        f.write(f'[metadata]\nadjusted = {"true" if adjusted else "false"}\nerror = {float(error)!r}\n')

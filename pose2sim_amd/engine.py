@@ -299,6 +299,52 @@ def write_timeline_csv(path, frame, person, slot, confidence, names, n_threads=0
                   _ptr(off), int(n_threads)))
 
 
+def _refine_extrinsics(lib, handle, xyl, K, R, t, X0, lik_thr, huber_px, min_cams, max_iter, ftol):
+    fn = _entry(lib, 'p2s_refine_extrinsics_host')
+    xyl = np.asarray(xyl)
+    if xyl.ndim < 3 or xyl.shape[-1] != 3:
+        raise P2sError(f'xyl has shape {xyl.shape}; expected [..., C, K, 3]')
+    Cn, Kn = xyl.shape[-3], xyl.shape[-2]
+    dtype = P2S_F32 if xyl.dtype == np.float32 else P2S_F64
+    # [..., C, K, 3] -> [points = (..., K)][C][3], the library's layout
+    pts = np.ascontiguousarray(np.moveaxis(xyl.reshape((-1, Cn, Kn, 3)), 1, 2).reshape(-1, Cn, 3),
+                               dtype=np.float32 if dtype == P2S_F32 else np.float64)
+    N = pts.shape[0]
+    K, R = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1, 9)) for v in (K, R))
+    t = np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1, 3))
+    X0 = np.ascontiguousarray(np.asarray(X0, dtype=np.float64).reshape(-1, 3))
+    if not (len(K) == len(R) == len(t) == Cn):
+        raise P2sError(f'K, R and t hold {len(K)}, {len(R)} and {len(t)} cameras; xyl has {Cn}')
+    if len(X0) != N:
+        raise P2sError(f'X0 holds {len(X0)} points; xyl has {N}')
+    prm = _lib.RefineParams(float(lik_thr), float(huber_px), float(ftol), int(min_cams), int(max_iter))
+    rep = _lib.RefineReport()
+    R_out, t_out, X_out = np.empty((Cn, 3, 3)), np.empty((Cn, 3)), np.empty((N, 3))
+    _lib.check(fn(handle, N, Cn, dtype, _ptr(pts), _ptr(K), _ptr(R), _ptr(t), _ptr(X0), C.byref(prm), _ptr(R_out), _ptr(t_out),
+                  _ptr(X_out), C.byref(rep)))
+    report = {'cost_before': rep.cost_before, 'cost_after': rep.cost_after, 'iterations': rep.iterations, 'accepted': rep.accepted,
+              'lambda': rep.lambda_final, 'kept_points': rep.kept_points, 'held_coord': rep.held_coord,
+              'rms_before': np.array(rep.rms_before[:Cn]), 'rms_after': np.array(rep.rms_after[:Cn])}
+    return R_out, t_out, X_out.reshape(xyl.shape[:-3] + (Kn, 3)), report
+
+
+def refine_extrinsics_host(xyl, K, R, t, X0, lik_thr=0.3, huber_px=3.0, min_cams=2, max_iter=100, ftol=1e-12):
+    """Engine.refine_extrinsics with the library's host path (no GPU): the same per-point functions, pass after pass."""
+    return _refine_extrinsics(_lib.load(), None, xyl, K, R, t, X0, lik_thr, huber_px, min_cams, max_iter, ftol)
+
+
+def refine_held_coord(R, t):
+    """The coordinate of camera 1's translation that refine_extrinsics holds: argmax_j |(t1 - R1 R0^T t0)_j|, the first
+    index on ties (host arithmetic of the library)."""
+    R = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(-1, 9)[:2])
+    t = np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1, 3)[:2])
+    if len(R) < 2 or len(t) < 2:
+        raise P2sError('the gauge needs two cameras')
+    j = C.c_int32(-1)
+    _lib.check(_entry(_lib.load(), 'p2s_refine_held_coord')(_ptr(R), _ptr(t), C.byref(j)))
+    return j.value
+
+
 class Engine:
     def __init__(self, device=0):
         self._lib = _lib.load()
@@ -993,6 +1039,20 @@ class Engine:
     def timeline_kernel_ms(self):
         """Kernel time of the last timeline_rows() call, from HIP events around its kernels."""
         return _kernel_ms(self, 'timeline')
+
+    # -- extrinsics refinement from keypoints (csrc/p2s_refine.hip, DESIGN.md 4.21) ---------------------------------------------
+    def refine_extrinsics(self, xyl, K, R, t, X0, lik_thr=0.3, huber_px=3.0, min_cams=2, max_iter=100, ftol=1e-12):
+        """Bundle adjustment of the cameras' R [C][3][3] and t [C][3] on xyl [F..., C, K, 3] (pinhole pixels and likelihood,
+        float32 or float64) from the start points X0 [prod(F...) * K][3], K [C][3][3] held: the Huber cost of the weighted
+        reprojection residuals over all cameras and points, camera 0 and one coordinate of camera 1's translation held
+        (include/p2s.h).  -> (R, t, X [F..., K, 3], report): X is NaN where a point was dropped; report holds
+        cost_before, cost_after, iterations, accepted, lambda, kept_points, held_coord, rms_before and rms_after [C] px."""
+        return _refine_extrinsics(self._lib, self._h, xyl, K, R, t, X0, lik_thr, huber_px, min_cams, max_iter, ftol)
+
+    def refine_kernel_ms(self):
+        """Time of the last refine_extrinsics() call between the HIP events around its kernels (the host's reduced solves
+        between the launches included)."""
+        return _kernel_ms(self, 'refine')
 
     # -- synchronization (synchronization.py:1271-1343, 1541-1585) -------------------------------------------------------
     def sync_speeds(self, coords, b, a, zi):
