@@ -918,6 +918,53 @@ int p2s_refine_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
 /* The held coordinate j of the gauge above from R_in and t_in of cameras 0 and 1 (host arithmetic, no context). */
 int p2s_refine_held_coord(const double *R_in, const double *t_in, int32_t *held);
 
+/* ---- relative poses of camera pairs from correspondences (csrc/p2s_relpose.hip) -----------------------
+ * The essential matrix of every camera pair out of contaminated correspondences: hypotheses from samples, MSAC scores,
+ * refits on the inliers, the cheirality count.  Host arrays in and out, fp64 throughout; ctx == NULL runs the same
+ * per-hypothesis and per-point functions on the host.
+ *   xn [n_cams][n_points][2] normalised pinhole coordinates (undistorted, K^-1 applied), usable [n_cams][n_points],
+ *   pairs [n_pairs][2] (a, b), samples [n_pairs][n_hyp][sample_size] point indices, thr2 [n_pairs] the squared Sampson
+ *   threshold in normalised units.  A point counts in a camera when it is usable there and both coordinates are finite;
+ *   the points of a pair are those that count in both of its cameras.
+ * Hypothesis of a sample: each side's points translated to their centroid and scaled to an RMS distance of sqrt 2, the
+ * sample_size x 9 system x_b'^T F' x_a' = 0, F' the eigenvector of the smallest eigenvalue of A^T A (first index on ties),
+ * F = Tb^T F' Ta, E = U diag(1, 1, 0) V^T of F's singular value decomposition; the sign of E is free.  A sample with a
+ * repeated index, an index outside [0, n_points) or a point that is not one of the pair's is refused, as is one whose F is
+ * not finite or has no two singular values above 0: E is NaN, the cost +inf, 0 inliers; the call does not fail.
+ * Score: d = (x_b^T E x_a)^2 / ((E x_a)_1^2 + (E x_a)_2^2 + (E^T x_b)_1^2 + (E^T x_b)_2^2) over the pair's points, or, with
+ * score_points > 0 and more points than that in some pair, over the pair's points of rank floor(i k / score_points), i = 0 ..
+ * score_points - 1, k the pair's count (every point of a pair with no more); a d that is not a number adds nothing.
+ * cost = sum min(d, thr2), inliers = the count of d < thr2; the winner has the lowest cost, the lowest index on ties.
+ * Then, over all of the pair's points: the winner's cost, and at most `rounds` refits: the 9 x 9 system of the inliers, with
+ * the same normalisation from the inliers' moments (centroid sum x / n, mean squared distance sum |x|^2 / n - |centroid|^2),
+ * is solved and projected as above; the refit is kept when its cost is lower, else the refits end; fewer than 8 inliers end
+ * them too.  The four (R, t) of E, X_b = R X_a + t, |t| = 1, in this order: (Ra, t), (Ra, -t), (Rb, t), (Rb, -t), where t has
+ * its largest coordinate (first on ties) positive and Ra is the rotation of the larger trace; front = the inliers with z_a >
+ * 0 and z_b > 0, z_a = -((x_b x R x_a) . (x_b x t)) / |x_b x R x_a|^2, z_b = (z_a R x_a + t)_3; the highest count wins, the
+ * first on ties.
+ * Out, per pair: E [9], R [9], t [3], cost, inliers, front, winner (the hypothesis' index), refits (those kept), mask
+ * [n_pairs][n_points] of the inliers.  A pair with fewer than sample_size points, or without a hypothesis of finite cost,
+ * is no error: NaN, counts 0, winner -1.  hyp_E [n_pairs][n_hyp][9], hyp_cost and hyp_inliers [n_pairs][n_hyp] (each may be
+ * NULL) receive every hypothesis.
+ * Refused with P2S_ERR_INVALID_ARG before any kernel runs: n_cams outside 2 .. P2S_MAX_CAMS, sample_size outside
+ * P2S_RELPOSE_MIN_SAMPLE .. P2S_RELPOSE_MAX_SAMPLE, n_hyp < 1, rounds < 0, a pair that names a camera twice or out of range,
+ * a thr2 that is not positive and finite.  Two calls on the same input return the same bits: every floating-point sum is
+ * taken in a fixed order (P2S_RELPOSE_TILE points a pass, at most P2S_RELPOSE_MAX_CHUNKS chunk sums a hypothesis and
+ * P2S_RELPOSE_MAX_PARTS partial sums a pair), the counts are integers. */
+#define P2S_RELPOSE_TILE 256
+#define P2S_RELPOSE_MAX_CHUNKS 64
+#define P2S_RELPOSE_MAX_PARTS 128
+#define P2S_RELPOSE_MIN_SAMPLE 8
+#define P2S_RELPOSE_MAX_SAMPLE 16
+int p2s_relative_poses_host(p2s_ctx *ctx, int32_t n_cams, int64_t n_points, const double *xn, const uint8_t *usable, int32_t n_pairs,
+                            const int32_t *pairs, int32_t n_hyp, int32_t sample_size, const int32_t *samples, const double *thr2,
+                            int32_t rounds, int32_t score_points, double *E_out, double *R_out, double *t_out, double *cost_out,
+                            int32_t *inliers_out, int32_t *front_out, int32_t *winner_out, int32_t *refits_out, uint8_t *mask_out,
+                            double *hyp_E, double *hyp_cost, int32_t *hyp_inliers);
+/* Milliseconds between the HIP events around this context's last p2s_relative_poses_host: its kernels and the eigen-solves
+ * of the refits on the host between them. */
+int p2s_relpose_kernel_ms(p2s_ctx *ctx, float *elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,8 @@ P2S_GAPS_NONFINITE = 1
 P2S_MEASURE_SPEED, P2S_MEASURE_ANGLES, P2S_MEASURE_RESTRICT, P2S_MEASURE_FEET_CONST, P2S_MEASURE_HEIGHT, P2S_MEASURE_LEG = 1, 2, 4, 8, 16, 32
 P2S_MEASURE_ALL_SLOW, P2S_MEASURE_FEW_SMALL_ANGLES, P2S_MEASURE_ALL_DATA = 1, 2, 4
 P2S_REFINE_TILE, P2S_REFINE_MAX_PARTS = 256, 128   # csrc/p2s_refine.hip: points a workgroup pass, partial sums a launch
+P2S_RELPOSE_TILE, P2S_RELPOSE_MAX_CHUNKS, P2S_RELPOSE_MAX_PARTS = 256, 64, 128   # csrc/p2s_relpose.hip: points a pass, chunk sums, partial sums
+P2S_RELPOSE_MIN_SAMPLE, P2S_RELPOSE_MAX_SAMPLE = 8, 16
 P2S_MEASURE_ROLES =('RShoulder', 'LShoulder', 'RHip', 'LHip', 'Hip', 'Neck', 'RKnee', 'LKnee', 'RAnkle', 'LAnkle')
 
 
@@ -158,6 +160,9 @@ SIGNATURES = {
                                    + [C.c_void_p] * 3 + [C.POINTER(RefineReport)]),
     'p2s_refine_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     'p2s_refine_held_coord': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    'p2s_relative_poses_host': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 12),
+    'p2s_relpose_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     'p2s_json_person_flags': (C.c_int, [C.c_void_p, C.c_void_p]),
     'p2s_write_person_files': (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     'p2s_find_peaks_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]
@@ -206,7 +211,8 @@ OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_h
             'p2s_track_select_kernel_ms', 'p2s_json_person_flags', 'p2s_write_person_files', 'p2s_track_persons_host',
             'p2s_track_persons_device', 'p2s_track_persons_kernel_ms', 'p2s_interpolate_gaps', 'p2s_fill_gaps', 'p2s_gap_runs',
             'p2s_gaps_kernel_ms', 'p2s_timeline_rows_host', 'p2s_timeline_kernel_ms', 'p2s_timeline_write_csv',
-            'p2s_refine_extrinsics_host', 'p2s_refine_kernel_ms', 'p2s_refine_held_coord'}
+            'p2s_refine_extrinsics_host', 'p2s_refine_kernel_ms', 'p2s_refine_held_coord', 'p2s_relative_poses_host',
+            'p2s_relpose_kernel_ms'}
 
 _lib = None
 

@@ -345,6 +345,39 @@ def refine_held_coord(R, t):
     return j.value
 
 
+def _relative_poses(lib, handle, xn, usable, pairs, samples, thr2, rounds, all_hypotheses, score_points):
+    fn = _entry(lib, 'p2s_relative_poses_host')
+    xn = np.ascontiguousarray(xn, dtype=np.float64)
+    if xn.ndim != 3 or xn.shape[-1] != 2:
+        raise P2sError(f'xn has shape {xn.shape}; expected [C][N][2]')
+    Cn, N = xn.shape[:2]
+    usable = np.ascontiguousarray(np.asarray(usable) != 0, dtype=np.uint8)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    samples = np.ascontiguousarray(samples, dtype=np.int32)
+    P = len(pairs)
+    thr2 = _per(thr2, P)
+    if usable.shape != (Cn, N):
+        raise P2sError(f'usable has shape {usable.shape}; expected {(Cn, N)}')
+    if samples.ndim != 3 or samples.shape[0] != P:
+        raise P2sError(f'samples has shape {samples.shape}; expected [{P}][H][m]')
+    H, m = samples.shape[1:]
+    out = {'E': np.empty((P, 3, 3)), 'R': np.empty((P, 3, 3)), 't': np.empty((P, 3)), 'cost': np.empty(P), 'inliers': np.empty(P, dtype=np.int32),
+           'front': np.empty(P, dtype=np.int32), 'winner': np.empty(P, dtype=np.int32), 'refits': np.empty(P, dtype=np.int32),
+           'mask': np.empty((P, N), dtype=np.uint8)}
+    if all_hypotheses:
+        out.update(hyp_E=np.empty((P, H, 3, 3)), hyp_cost=np.empty((P, H)), hyp_inliers=np.empty((P, H), dtype=np.int32))
+    _lib.check(fn(handle, Cn, N, _ptr(xn), _ptr(usable), P, _ptr(pairs), H, m, _ptr(samples), _ptr(thr2), int(rounds), int(score_points),
+                  *[_ptr(out[k]) for k in ('E', 'R', 't', 'cost', 'inliers', 'front', 'winner', 'refits', 'mask')],
+                  *[_ptr(out.get(k)) for k in ('hyp_E', 'hyp_cost', 'hyp_inliers')]))
+    out['mask'] = out['mask'].view(bool)
+    return out
+
+
+def relative_poses_host(xn, usable, pairs, samples, thr2, rounds=3, all_hypotheses=False, score_points=0):
+    """Engine.relative_poses with the library's host path (no GPU): the same per-hypothesis and per-point functions."""
+    return _relative_poses(_lib.load(), None, xn, usable, pairs, samples, thr2, rounds, all_hypotheses, score_points)
+
+
 class Engine:
     def __init__(self, device=0):
         self._lib = _lib.load()
@@ -1053,6 +1086,21 @@ class Engine:
         """Time of the last refine_extrinsics() call between the HIP events around its kernels (the host's reduced solves
         between the launches included)."""
         return _kernel_ms(self, 'refine')
+
+    # -- relative poses of camera pairs (csrc/p2s_relpose.hip, DESIGN.md 4.22) ---------------------------------------------------
+    def relative_poses(self, xn, usable, pairs, samples, thr2, rounds=3, all_hypotheses=False, score_points=0):
+        """The essential matrix and (R, t), X_b = R X_a + t with |t| = 1, of every camera pair by hypothesise and score.
+        xn [C][N][2] normalised pinhole coordinates, usable [C][N], pairs [P][2], samples [P][H][m] point indices (8 <= m <=
+        16), thr2 the squared Sampson threshold in normalised units (one, or one a pair); the hypotheses are scored on at
+        most score_points evenly spaced points of a pair (0: all), the refits (at most `rounds`) use all.
+        -> dict: E [P][3][3], R, t [P][3], cost, inliers, front, winner, refits [P], mask [P][N]; with all_hypotheses also
+        hyp_E [P][H][3][3], hyp_cost, hyp_inliers [P][H].  A pair without a result has NaN, counts 0 and winner -1."""
+        return _relative_poses(self._lib, self._h, xn, usable, pairs, samples, thr2, rounds, all_hypotheses, score_points)
+
+    def relpose_kernel_ms(self):
+        """Time of the last relative_poses() call between the HIP events around its kernels (the refits' eigen-solves on the
+        host between them included)."""
+        return _kernel_ms(self, 'relpose')
 
     # -- synchronization (synchronization.py:1271-1343, 1541-1585) -------------------------------------------------------
     def sync_speeds(self, coords, b, a, zi):
