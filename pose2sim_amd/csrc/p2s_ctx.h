@@ -1,8 +1,8 @@
 // p2s_ctx.h -- the per-GPU context behind include/p2s.h's opaque p2s_ctx, and what the C-ABI entry points (p2s_api.hip
 // and the tail of every stage's kernel file) share to use it: HIP_TRY / P2S_TRY, the grow-only Scratch buffer, Stage,
 // which hands a *_host call its device buffers and times its kernels (one slot of p2s_ctx::kernel_ms a stage, read
-// back by p2s_kernel_ms_query), Layout, which carves one block into arrays, and the checked frame and person offsets
-// of the per-camera analysis stages (P2sFrames).
+// back by p2s_kernel_ms_query), Layout, which carves one block into arrays, Block, which keeps that block on the device
+// or on the host, and the checked frame and person offsets of the per-camera analysis stages (P2sFrames).
 #ifndef P2S_CTX_H
 #define P2S_CTX_H
 
@@ -151,6 +151,42 @@ struct Layout {
         bytes += (n + 15) / 16 * 16;
         return at;
     }
+};
+
+// One Layout block of a call that runs the same code on the device or, ctx == NULL, on the host: a Stage buffer there, the
+// host's own memory here.  put and get copy into and out of it (on the device async: what they name lives until wait());
+// the timer does nothing on the host.
+struct Block {
+    Stage st;
+    char *p = nullptr;
+    std::vector<char> host;
+    int alloc(size_t bytes) {
+        if (st.ctx) return st.alloc(p, bytes);
+        host.resize(bytes);
+        p = host.data();
+        return P2S_OK;
+    }
+    int put(void *d, const void *h, size_t bytes) const {
+        if (st.ctx) return st.up(d, h, bytes);
+        if (bytes) memcpy(d, h, bytes);
+        return P2S_OK;
+    }
+    int put_wait(void *d, const void *h, size_t bytes) const {        // h may change when this returns
+        P2S_TRY(put(d, h, bytes));
+        return wait();
+    }
+    int get(void *h, const void *d, size_t bytes) const {             // a NULL h is skipped
+        if (st.ctx) return st.down(h, d, bytes);
+        if (h && bytes) memcpy(h, d, bytes);
+        return P2S_OK;
+    }
+    int wait() const {
+        if (st.ctx) HIP_TRY(hipStreamSynchronize(st.ctx->stream));
+        return P2S_OK;
+    }
+    int time_begin() const { return st.ctx ? st.time_begin() : P2S_OK; }
+    int time_end() const { return st.ctx ? st.time_end() : P2S_OK; }
+    int finish(int which) const { return st.ctx ? st.finish(which) : P2S_OK; }
 };
 
 // The cameras of a per-camera analysis call (jitter, confidence, id_switch, track_select), frames back to back.

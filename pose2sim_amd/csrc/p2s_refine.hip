@@ -8,14 +8,16 @@
 //                      Y_c = W_c L^-T; per (pass, camera): U_c, g_c and W_c V^-1 gp.  The hot path: 3 N C (C + 1) / 2 x 36
 //                      multiply-adds, blocked by camera pairs because the 6C x 6C triangle of 32 cameras (148 KB) leaves a
 //                      workgroup no other LDS and a CU no second workgroup
-//   rf_step_kernel     per point: dX = -V^-1 (gp + sum_c W_c^T dc_c), the trial point, the trial's Huber cost
-//   rf_stats_kernel    per (pass, camera): cost, sum s^2 d^2, sum s^2 (the report's RMS)
-//   rf_sum_kernel      the partial sums of a launch, added in a fixed order
+//   RfStep             a pass of p2s_passes.h, per point: dX = -V^-1 (gp + sum_c W_c^T dc_c), the trial point, the trial's
+//                      Huber cost
+//   RfStats            a pass, per (part of the points, camera): cost, sum s^2 d^2, sum s^2 (the report's RMS)
+//   rf_sum_kernel      (p2s_passes.h) the partial sums of a launch, added in a fixed order
 //
 // No floating-point atomic anywhere: a lane adds its points in order, a wave adds its lanes by the xor butterfly, a
-// workgroup its waves in order, rf_sum_kernel the workgroups' partial sums in order.  Two runs agree bit for bit.
-// The trial cameras R <- exp([dw]x) R, t <- t + dt are formed on the host next to the reduced solve (at most 185
-// unknowns) and go up with dc.  ctx == NULL runs the same per-point functions on the host, pass after pass.
+// workgroup its waves in order (p2s_block_sum), rf_sum_kernel the workgroups' partial sums in order.  Two runs agree bit
+// for bit.  The trial cameras R <- exp([dw]x) R, t <- t + dt are formed on the host next to the reduced solve (at most
+// 185 unknowns) and go up with dc.  ctx == NULL runs the same per-point functions on the host, pass after pass
+// (p2s_pass_host, the parts then added in order), in a Block of the host's memory.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -25,6 +27,7 @@
 #include <vector>
 
 #include "p2s_ctx.h"
+#include "p2s_passes.h"
 
 #define RF_HD __host__ __device__ inline
 
@@ -332,22 +335,21 @@ RF_HD void rf_stats_point(const P2sRfArgs &a, int64_t n, int c, double acc[3]) {
     acc[2] += s * s;
 }
 
-// ---- kernels ----------------------------------------------------------------------------------------------------------------
-// The workgroup's sum of W values a lane: lanes by the butterfly, waves in order; out[i * stride] for value i.
-template <int W> __device__ void rf_block_sum(double (&acc)[W], double *lds, double *out, int64_t stride) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = 0; i < W; ++i) {
-        double v = acc[i];
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-        if (lane == 0) lds[wave * W + i] = v;
+// ---- the passes and the kernels ----------------------------------------------------------------------------------------
+struct RfBlocks : P2sPassAll {                                     // row y: rf_row; the host's form of rf_blocks_kernel
+    RF_HD static void point(const P2sRfArgs &a, int y, int64_t n, double *acc) {
+        int ca, cb;
+        rf_row(a.C, y, ca, cb);
+        if (cb >= 0) rf_pair_point(a, n, ca, cb, acc);
+        else rf_cam_point(a, n, ca, acc);
     }
-    __syncthreads();
-    if (tid < W) {
-        double s = 0.0;
-        for (int w = 0; w < TILE / 64; ++w) s += lds[w * W + tid];
-        out[tid * stride] = s;
-    }
-}
+};
+struct RfStep : P2sPassAll {                                       // one row
+    RF_HD static void point(const P2sRfArgs &a, int, int64_t n, double *acc) { acc[0] += rf_step_point(a, n); }
+};
+struct RfStats : P2sPassAll {                                      // row c: a camera
+    RF_HD static void point(const P2sRfArgs &a, int c, int64_t n, double *acc) { rf_stats_point(a, n, c, acc); }
+};
 
 struct RfPrepArgs {
     const void *xyl;
@@ -386,6 +388,8 @@ __global__ void __launch_bounds__(TILE) rf_point_kernel(const P2sRfArgs a) {
     if (n < a.N) rf_point_build(a, n);
 }
 
+// RfBlocks with rf_row ahead of the points, written out: at the register limit (256 VGPRs, no scratch) any function between
+// this body and the two per-point functions, p2s_pass_kernel<NACC, TILE, RfBlocks> included, is allocated otherwise.
 __global__ void __launch_bounds__(TILE) rf_blocks_kernel(const P2sRfArgs a) {
     __shared__ double lds[(TILE / 64) * NACC];
     int ca, cb;
@@ -398,68 +402,27 @@ __global__ void __launch_bounds__(TILE) rf_blocks_kernel(const P2sRfArgs a) {
         if (cb >= 0) rf_pair_point(a, n, ca, cb, acc);
         else rf_cam_point(a, n, ca, acc);
     }
-    rf_block_sum<NACC>(acc, lds, a.partials + (int64_t)blockIdx.y * NACC * a.parts + blockIdx.x, a.parts);
-}
-
-__global__ void __launch_bounds__(TILE) rf_step_kernel(const P2sRfArgs a) {
-    __shared__ double lds[TILE / 64];
-    double acc[1] = {0.0};
-    for (int64_t t = blockIdx.x; t < a.tiles; t += a.parts) {
-        const int64_t n = t * TILE + threadIdx.x;
-        if (n < a.N) acc[0] += rf_step_point(a, n);
-    }
-    rf_block_sum<1>(acc, lds, a.partials + blockIdx.x, a.parts);
-}
-
-__global__ void __launch_bounds__(TILE) rf_stats_kernel(const P2sRfArgs a) {
-    __shared__ double lds[(TILE / 64) * 3];
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (int64_t t = blockIdx.x; t < a.tiles; t += a.parts) {
-        const int64_t n = t * TILE + threadIdx.x;
-        if (n < a.N) rf_stats_point(a, n, blockIdx.y, acc);
-    }
-    rf_block_sum<3>(acc, lds, a.partials + (int64_t)blockIdx.y * 3 * a.parts + blockIdx.x, a.parts);
-}
-
-// One wave a value: lane l adds the partial sums l, l + 64, .. in order, the lanes by the butterfly.
-__global__ void __launch_bounds__(64) rf_sum_kernel(const double *partials, double *sums, int parts) {
-    const double *p = partials + (int64_t)blockIdx.x * parts;
-    double v = 0.0;
-    for (int i = threadIdx.x; i < parts; i += 64) v += p[i];
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if (threadIdx.x == 0) sums[blockIdx.x] = v;
-}
-
-// ---- the same passes on the host ------------------------------------------------------------------------------------------
-// rows x width values: fn(n, row, acc) over the points of every part in the kernels' order, then the parts in order.
-template <int W, typename F> void rf_host_sum(const P2sRfArgs &a, int rows, double *sums, F fn) {
-    for (int y = 0; y < rows; ++y) {
-        double total[W] = {};
-        for (int p = 0; p < a.parts; ++p) {
-            double acc[W] = {};
-            for (int64_t t = p; t < a.tiles; t += a.parts)
-                for (int64_t n = t * TILE; n < std::min<int64_t>(a.N, (t + 1) * TILE); ++n) fn(n, y, acc);
-            for (int i = 0; i < W; ++i) total[i] += acc[i];
-        }
-        for (int i = 0; i < W; ++i) sums[y * W + i] = total[i];
-    }
+    p2s_block_sum<NACC, TILE>(acc, lds, a.partials + (int64_t)blockIdx.y * NACC * a.parts + blockIdx.x, a.parts);
 }
 
 // ---- the driver ---------------------------------------------------------------------------------------------------------------
 struct RfRun {
     p2s_ctx *ctx;                // NULL: on the host
-    const Stage *st;
+    const Block *block;
     P2sRfArgs a;
     std::vector<double> sums;    // the host's copy of a.sums
     int rows() const { return a.C * (a.C + 1) / 2 + a.C; }
 
+    // sums [width] of the pass that a.partials holds
     int fetch(size_t width) {
-        if (!ctx) return P2S_OK;
+        if (!ctx) {
+            p2s_sum_parts(a.partials, width, a.parts, sums.data());
+            return P2S_OK;
+        }
         hipLaunchKernelGGL(rf_sum_kernel, dim3((unsigned)width), dim3(64), 0, ctx->stream, a.partials, a.sums, a.parts);
         HIP_TRY(hipGetLastError());
-        P2S_TRY(st->down(sums.data(), a.sums, width * 8));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return P2S_OK;
+        P2S_TRY(block->get(sums.data(), a.sums, width * 8));
+        return block->wait();
     }
     // sums [rows][36]: the Schur blocks of the camera pairs, then U, g, W V^-1 gp of the cameras
     int build(double lambda) {
@@ -470,47 +433,22 @@ struct RfRun {
             hipLaunchKernelGGL(rf_blocks_kernel, dim3((unsigned)a.parts, (unsigned)rows()), dim3(TILE), 0, ctx->stream, a);
         } else {
             for (int64_t n = 0; n < a.N; ++n) rf_point_build(a, n);
-            const P2sRfArgs &b = a;
-            rf_host_sum<NACC>(a, rows(), sums.data(), [&b](int64_t n, int y, double *acc) {
-                int ca, cb;
-                rf_row(b.C, y, ca, cb);
-                if (cb >= 0) rf_pair_point(b, n, ca, cb, acc);
-                else rf_cam_point(b, n, ca, acc);
-            });
+            p2s_pass_host<NACC, TILE, RfBlocks>(a, rows());
         }
         return fetch((size_t)rows() * NACC);
     }
     // The trial (move: X + dX at cams_t; else X itself): Xt and its cost.
     int step(int move, double *cost) {
         a.move = move;
-        if (ctx) {
-            hipLaunchKernelGGL(rf_step_kernel, dim3((unsigned)a.parts), dim3(TILE), 0, ctx->stream, a);
-        } else {
-            const P2sRfArgs &b = a;
-            rf_host_sum<1>(a, 1, sums.data(), [&b](int64_t n, int, double *acc) { acc[0] += rf_step_point(b, n); });
-        }
+        P2S_TRY((p2s_pass<1, TILE, RfStep>(ctx, a, 1)));
         P2S_TRY(fetch(1));
         *cost = sums[0];
         return P2S_OK;
     }
     // sums [C][3] at a.cams and a.X
     int stats() {
-        if (ctx) {
-            hipLaunchKernelGGL(rf_stats_kernel, dim3((unsigned)a.parts, (unsigned)a.C), dim3(TILE), 0, ctx->stream, a);
-        } else {
-            const P2sRfArgs &b = a;
-            rf_host_sum<3>(a, a.C, sums.data(), [&b](int64_t n, int c, double *acc) { rf_stats_point(b, n, c, acc); });
-        }
+        P2S_TRY((p2s_pass<3, TILE, RfStats>(ctx, a, a.C)));
         return fetch((size_t)a.C * 3);
-    }
-    int put(const double *d, const double *h, size_t count) const {  // a small table of the host's, up (or across)
-        if (!ctx) {
-            memcpy((void *)d, h, count * 8);
-            return P2S_OK;
-        }
-        P2S_TRY(st->up(d, h, count * 8));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));                   // h may change when this returns
-        return P2S_OK;
     }
 };
 
@@ -668,7 +606,8 @@ int p2s_refine_extrinsics_host(p2s_ctx *ctx, int64_t n_points, int32_t n_cams, i
         for (int k = 0; k < 6; ++k)
             if (!(c == 1 && k == 3 + held)) free_idx.push_back(6 * c + k);
 
-    RfRun run{ctx, nullptr, {}, {}};
+    Block block{Stage{ctx}};
+    RfRun run{ctx, &block, {}, {}};
     P2sRfArgs &a = run.a;
     a.N = n_points; a.C = C; a.delta = params->huber_px;
     a.tiles = (int32_t)((n_points + TILE - 1) / TILE);
@@ -680,45 +619,35 @@ int p2s_refine_extrinsics_host(p2s_ctx *ctx, int64_t n_points, int32_t n_cams, i
                  o_count = lay.add(P2S_MAX_CAMS * 4), o_ctr = lay.add(16), o_sums = lay.add(width * 8),
                  o_parts = lay.add(width * (size_t)a.parts * 8), o_kept = lay.add(N), o_ou = lay.add(N * C * 8), o_ov = lay.add(N * C * 8),
                  o_os = lay.add(N * C * 8), o_x = lay.add(N * 24), o_xt = lay.add(N * 24), o_pt = lay.add(N * 72), o_x0 = lay.add(N * 24);
-    std::vector<char> host_block;
-    Stage st{ctx};
-    run.st = &st;
-    char *blk;
     const void *d_xyl = xyl;
     unsigned int cam_count[P2S_MAX_CAMS] = {};
     unsigned long long counters[2] = {0, ~0ull};
     if (ctx) {
         HIP_TRY(hipSetDevice(ctx->device));
-        P2S_TRY(st.upload(d_xyl, xyl, N * C * 3 * (dtype == P2S_F32 ? 4 : 8)));
-        P2S_TRY(st.alloc(blk, lay.bytes));
-        P2S_TRY(st.up(blk + o_x0, X0, N * 24));
-        P2S_TRY(st.up(blk + o_cams, cams.data(), cams.size() * 8));
-        P2S_TRY(st.up(blk + o_camst, cams.data(), cams.size() * 8));
-        P2S_TRY(st.up(blk + o_dc, dc.data(), dc.size() * 8));
-        P2S_TRY(st.up(blk + o_count, cam_count, sizeof cam_count));
-        P2S_TRY(st.up(blk + o_ctr, counters, sizeof counters));
-    } else {
-        host_block.resize(lay.bytes);
-        blk = host_block.data();
-        memcpy(blk + o_x0, X0, N * 24);
-        memcpy(blk + o_cams, cams.data(), cams.size() * 8);
-        memcpy(blk + o_camst, cams.data(), cams.size() * 8);
-        memcpy(blk + o_dc, dc.data(), dc.size() * 8);
+        P2S_TRY(block.st.upload(d_xyl, xyl, N * C * 3 * (dtype == P2S_F32 ? 4 : 8)));
     }
+    P2S_TRY(block.alloc(lay.bytes));
+    char *blk = block.p;
+    P2S_TRY(block.put(blk + o_x0, X0, N * 24));
+    P2S_TRY(block.put(blk + o_cams, cams.data(), cams.size() * 8));
+    P2S_TRY(block.put(blk + o_camst, cams.data(), cams.size() * 8));
+    P2S_TRY(block.put(blk + o_dc, dc.data(), dc.size() * 8));
+    P2S_TRY(block.put(blk + o_count, cam_count, sizeof cam_count));
+    P2S_TRY(block.put(blk + o_ctr, counters, sizeof counters));
     double *d_cams[2] = {(double *)(blk + o_cams), (double *)(blk + o_camst)}, *d_X[2] = {(double *)(blk + o_x), (double *)(blk + o_xt)};
     double *d_dc = (double *)(blk + o_dc);
     a.ou = (double *)(blk + o_ou); a.ov = (double *)(blk + o_ov); a.os = (double *)(blk + o_os); a.kept = (uint8_t *)(blk + o_kept);
     a.pt = (double *)(blk + o_pt); a.dc = d_dc; a.partials = (double *)(blk + o_parts); a.sums = (double *)(blk + o_sums);
     RfPrepArgs p{d_xyl, (const double *)(blk + o_x0), d_cams[0], (double *)a.ou, (double *)a.ov, (double *)a.os, d_X[0], (uint8_t *)a.kept,
                  (unsigned int *)(blk + o_count), (unsigned long long *)(blk + o_ctr), n_points, C, min_cams, params->lik_thr};
+    P2S_TRY(block.time_begin());
     if (ctx) {
-        P2S_TRY(st.time_begin());
         if (dtype == P2S_F32) hipLaunchKernelGGL(rf_prep_kernel<float>, dim3((unsigned)a.tiles), dim3(TILE), 0, ctx->stream, p);
         else hipLaunchKernelGGL(rf_prep_kernel<double>, dim3((unsigned)a.tiles), dim3(TILE), 0, ctx->stream, p);
         HIP_TRY(hipGetLastError());
-        P2S_TRY(st.down(cam_count, p.cam_count, sizeof cam_count));
-        P2S_TRY(st.down(counters, p.counters, sizeof counters));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        P2S_TRY(block.get(cam_count, p.cam_count, sizeof cam_count));
+        P2S_TRY(block.get(counters, p.counters, sizeof counters));
+        P2S_TRY(block.wait());
     } else {
         for (int64_t n = 0; n < n_points; ++n) {
             int behind;
@@ -756,8 +685,8 @@ int p2s_refine_extrinsics_host(p2s_ctx *ctx, int64_t n_points, int32_t n_cams, i
         double trial = __builtin_huge_val();
         if (rf_solve_cameras(run.sums, C, lambda, free_idx, dc)) {
             for (int c = 0; c < C; ++c) rf_move_camera(&cams[(size_t)c * CAMW], &dc[(size_t)c * 6], &cams_t[(size_t)c * CAMW]);
-            P2S_TRY(run.put(d_dc, dc.data(), dc.size()));
-            P2S_TRY(run.put(d_cams[cur ^ 1], cams_t.data(), cams_t.size()));
+            P2S_TRY(block.put_wait(d_dc, dc.data(), dc.size() * 8));
+            P2S_TRY(block.put_wait(d_cams[cur ^ 1], cams_t.data(), cams_t.size() * 8));
             P2S_TRY(run.step(1, &trial));
         }
         if (trial < cost) {
@@ -780,13 +709,9 @@ int p2s_refine_extrinsics_host(p2s_ctx *ctx, int64_t n_points, int32_t n_cams, i
     a.cams = a.cams_t = d_cams[cur]; a.X = d_X[xcur]; a.Xt = d_X[xcur ^ 1];
     P2S_TRY(run.stats());
     rf_rms(run.sums, C, rep.rms_after);
-    if (ctx) {
-        P2S_TRY(st.time_end());
-        P2S_TRY(st.down(X_out, d_X[xcur], N * 24));
-        P2S_TRY(st.finish(P2S_TIMED_REFINE));
-    } else {
-        memcpy(X_out, d_X[xcur], N * 24);
-    }
+    P2S_TRY(block.time_end());
+    P2S_TRY(block.get(X_out, d_X[xcur], N * 24));
+    P2S_TRY(block.finish(P2S_TIMED_REFINE));
     for (int c = 0; c < C; ++c) {
         memcpy(R_out + c * 9, &cams[(size_t)c * CAMW + 4], 72);
         memcpy(t_out + c * 3, &cams[(size_t)c * CAMW + 13], 24);

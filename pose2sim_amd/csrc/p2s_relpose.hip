@@ -11,14 +11,16 @@
 //                     in registers, the workgroup streams the pair's points through LDS, 256 at a time, every lane reads
 //                     the same point (a broadcast); P x H x N Sampson distances
 //   rp_winner_kernel  per pair: the chunk sums of every hypothesis added in order, the lowest cost (lowest index on ties)
-//   rp_stat_kernel    per (pair, part of the points), one lane a point, the pair's current E: cost, inliers and the inliers'
-//                     moments;  rp_normal_kernel: the 45 sums of the inliers' normal matrix;  rp_front_kernel: the inlier
-//                     mask and, per (R, t) candidate, the inliers in front of both cameras
+//   RpStat            a pass of p2s_passes.h, per (pair, part of the points), one lane a point, the pair's current E: cost,
+//                     inliers and the inliers' moments;  RpNormal: the 45 sums of the inliers' normal matrix; both leave
+//                     out the pairs that are not active
+//   rp_front_kernel   the inlier mask and, per (R, t) candidate, the inliers in front of both cameras
 //
 // No floating-point atomic anywhere: a lane adds its points in order, a wave its lanes by the xor butterfly, a workgroup its
-// waves in order, the host the parts (and rp_winner_kernel the chunks) in order; counts are integers.  Two runs agree bit
-// for bit.  The 9 x 9 eigen-solves of the refits and the decompositions run on the host between the launches, with the
-// functions the kernels use.  ctx == NULL runs the same per-hypothesis and per-point functions on the host.
+// waves in order (p2s_block_sum), the host the parts (and rp_winner_kernel the chunks) in order; counts are integers.  Two
+// runs agree bit for bit.  The 9 x 9 eigen-solves of the refits and the decompositions run on the host between the
+// launches, with the functions the kernels use.  ctx == NULL runs the same per-hypothesis and per-point functions on the
+// host (the passes as p2s_pass_host), in a Block of the host's memory.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -28,6 +30,7 @@
 #include <vector>
 
 #include "p2s_ctx.h"
+#include "p2s_passes.h"
 
 #define RP_HD __host__ __device__ inline
 
@@ -444,49 +447,16 @@ __global__ void __launch_bounds__(TILE) rp_winner_kernel(const RpArgs a) {
     if (tid < 9) a.winE[p * 9 + tid] = a.winner[p] >= 0 ? a.hypE[((int64_t)p * a.H + a.winner[p]) * 9 + tid] : rp_nan();
 }
 
-// The workgroup's sum of W values a lane: lanes by the butterfly, waves in order; out[i * stride] for value i.
-template <int W> __device__ void rp_block_sum(double (&acc)[W], double *lds, double *out, int64_t stride) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int i = 0; i < W; ++i) {
-        double v = acc[i];
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-        if (lane == 0) lds[wave * W + i] = v;
-    }
-    __syncthreads();
-    if (tid < W) {
-        double s = 0.0;
-        for (int w = 0; w < TILE / 64; ++w) s += lds[w * W + tid];
-        out[tid * stride] = s;
-    }
-}
-
-__global__ void __launch_bounds__(TILE) rp_stat_kernel(const RpArgs a) {
-    __shared__ double lds[(TILE / 64) * NSTAT];
-    const int p = blockIdx.y;
-    if (!a.active[p]) return;                                        // uniform over the workgroup
-    double acc[NSTAT];
-    for (int i = 0; i < NSTAT; ++i) acc[i] = 0.0;
-    for (int64_t t = blockIdx.x; t < a.tiles; t += a.parts) {
-        const int64_t n = t * TILE + threadIdx.x;
-        if (n < a.N) rp_stat_point(a, p, n, acc);
-    }
-    rp_block_sum<NSTAT>(acc, lds, a.partials + (int64_t)p * NSTAT * a.parts + blockIdx.x, a.parts);
-}
-
-__global__ void __launch_bounds__(TILE) rp_normal_kernel(const RpArgs a) {
-    __shared__ double lds[(TILE / 64) * NSYM];
-    const int p = blockIdx.y;
-    if (!a.active[p]) return;
-    double acc[NSYM];
-#pragma unroll
-    for (int i = 0; i < NSYM; ++i) acc[i] = 0.0;
-    for (int64_t t = blockIdx.x; t < a.tiles; t += a.parts) {
-        const int64_t n = t * TILE + threadIdx.x;
-        if (n < a.N) rp_normal_point(a, p, n, acc);
-    }
-    rp_block_sum<NSYM>(acc, lds, a.partials + (int64_t)p * NSYM * a.parts + blockIdx.x, a.parts);
-}
+// The per-point passes: row p, a pair.
+struct RpActive {
+    RP_HD static bool skip(const RpArgs &a, int p) { return !a.active[p]; }
+};
+struct RpStat : RpActive {
+    RP_HD static void point(const RpArgs &a, int p, int64_t n, double *acc) { rp_stat_point(a, p, n, acc); }
+};
+struct RpNormal : RpActive {
+    RP_HD static void point(const RpArgs &a, int p, int64_t n, double *acc) { rp_normal_point(a, p, n, acc); }
+};
 
 __global__ void __launch_bounds__(TILE) rp_front_kernel(const RpArgs a) {
     __shared__ unsigned int cnt[4];
@@ -549,46 +519,17 @@ void rp_decompose(const double E[9], double cand[48]) {
 
 struct RpRun {
     p2s_ctx *ctx;
-    const Stage *st;
+    const Block *block;
     RpArgs a;
     std::vector<double> partials;          // the host's copy
-    int put(const void *d, const void *h, size_t bytes) const {
-        if (!ctx) {
-            memcpy((void *)d, h, bytes);
-            return P2S_OK;
-        }
-        P2S_TRY(st->up(d, h, bytes));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return P2S_OK;
-    }
-    // sums [P][W] of fn over the points of the active pairs: parts in order
-    template <int W, typename K, typename F> int sums(K kernel, F fn, const std::vector<uint8_t> &active, std::vector<double> &out) {
-        const int parts = a.parts;
-        if (ctx) {
-            hipLaunchKernelGGL(kernel, dim3((unsigned)parts, (unsigned)a.P), dim3(TILE), 0, ctx->stream, a);
-            HIP_TRY(hipGetLastError());
-            P2S_TRY(st->down(partials.data(), a.partials, (size_t)a.P * W * parts * 8));
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-        } else {
-            for (int p = 0; p < a.P; ++p) {
-                if (!active[p]) continue;
-                for (int part = 0; part < parts; ++part) {
-                    double acc[W] = {};
-                    for (int64_t t = part; t < a.tiles; t += parts)
-                        for (int64_t n = t * TILE; n < std::min<int64_t>(a.N, (t + 1) * TILE); ++n) fn(a, p, n, acc);
-                    for (int i = 0; i < W; ++i) partials[((size_t)p * W + i) * parts + part] = acc[i];
-                }
-            }
-        }
+    // sums [P][W] of the pass F over the points of the active pairs: parts in order
+    template <int W, typename F> int sums(const std::vector<uint8_t> &active, std::vector<double> &out) {
+        P2S_TRY((p2s_pass<W, TILE, F>(ctx, a, a.P)));
+        P2S_TRY(block->get(partials.data(), a.partials, (size_t)a.P * W * a.parts * 8));
+        P2S_TRY(block->wait());
         out.assign((size_t)a.P * W, 0.0);
-        for (int p = 0; p < a.P; ++p) {
-            if (!active[p]) continue;
-            for (int i = 0; i < W; ++i) {
-                double s = 0.0;
-                for (int part = 0; part < parts; ++part) s += partials[((size_t)p * W + i) * parts + part];
-                out[(size_t)p * W + i] = s;
-            }
-        }
+        for (int p = 0; p < a.P; ++p)
+            if (active[p]) p2s_sum_parts(&partials[(size_t)p * W * a.parts], W, a.parts, &out[(size_t)p * W]);
         return P2S_OK;
     }
 };
@@ -653,7 +594,8 @@ int p2s_relative_poses_host(p2s_ctx *ctx, int32_t n_cams, int64_t n_points, cons
         }
     }
 
-    RpRun run{ctx, nullptr, {}, {}};
+    Block block{Stage{ctx}};
+    RpRun run{ctx, &block, {}, {}};
     RpArgs &a = run.a;
     a.N = N; a.P = P; a.H = H; a.m = m; a.S = S;
     a.tiles = (int32_t)((N + TILE - 1) / TILE);
@@ -670,34 +612,17 @@ int p2s_relative_poses_host(p2s_ctx *ctx, int32_t n_cams, int64_t n_points, cons
                  o_nlist = lay.add((size_t)P * 4), o_parts = lay.add(n_partials * 8), o_xn = lay.add((size_t)C * N * 16), o_ok = lay.add((size_t)C * N),
                  o_smp = lay.add(PH * m * 4), o_hE = lay.add(PH * 72), o_pc = lay.add(PH * chunks * 8), o_pi = lay.add(PH * chunks * 4),
                  o_hc = lay.add(PH * 8), o_hi = lay.add(PH * 4), o_list = lay.add((size_t)P * S * 4), o_mask = lay.add((size_t)P * N);
-    std::vector<char> host_block;
-    Stage st{ctx};
-    run.st = &st;
-    char *blk;
-    if (ctx) {
-        HIP_TRY(hipSetDevice(ctx->device));
-        P2S_TRY(st.alloc(blk, lay.bytes));
-        P2S_TRY(st.up(blk + o_pairs, pairs, (size_t)P * 8));
-        P2S_TRY(st.up(blk + o_thr, thr2, (size_t)P * 8));
-        P2S_TRY(st.up(blk + o_xn, xn, (size_t)C * N * 16));
-        P2S_TRY(st.up(blk + o_ok, ok.data(), ok.size()));
-        P2S_TRY(st.up(blk + o_smp, samples, PH * m * 4));
-        if (S) {
-            P2S_TRY(st.up(blk + o_nlist, n_list.data(), (size_t)P * 4));
-            P2S_TRY(st.up(blk + o_list, list.data(), list.size() * 4));
-        }
-    } else {
-        host_block.resize(lay.bytes);
-        blk = host_block.data();
-        memcpy(blk + o_pairs, pairs, (size_t)P * 8);
-        memcpy(blk + o_thr, thr2, (size_t)P * 8);
-        memcpy(blk + o_xn, xn, (size_t)C * N * 16);
-        memcpy(blk + o_ok, ok.data(), ok.size());
-        memcpy(blk + o_smp, samples, PH * m * 4);
-        if (S) {
-            memcpy(blk + o_nlist, n_list.data(), (size_t)P * 4);
-            memcpy(blk + o_list, list.data(), list.size() * 4);
-        }
+    if (ctx) HIP_TRY(hipSetDevice(ctx->device));
+    P2S_TRY(block.alloc(lay.bytes));
+    char *blk = block.p;
+    P2S_TRY(block.put(blk + o_pairs, pairs, (size_t)P * 8));
+    P2S_TRY(block.put(blk + o_thr, thr2, (size_t)P * 8));
+    P2S_TRY(block.put(blk + o_xn, xn, (size_t)C * N * 16));
+    P2S_TRY(block.put(blk + o_ok, ok.data(), ok.size()));
+    P2S_TRY(block.put(blk + o_smp, samples, PH * m * 4));
+    if (S) {
+        P2S_TRY(block.put(blk + o_nlist, n_list.data(), (size_t)P * 4));
+        P2S_TRY(block.put(blk + o_list, list.data(), list.size() * 4));
     }
     a.xn = (const double *)(blk + o_xn); a.ok = (const uint8_t *)(blk + o_ok); a.pairs = (const int32_t *)(blk + o_pairs);
     a.samples = (const int32_t *)(blk + o_smp); a.thr2 = (const double *)(blk + o_thr); a.hypE = (double *)(blk + o_hE);
@@ -712,18 +637,12 @@ int p2s_relative_poses_host(p2s_ctx *ctx, int32_t n_cams, int64_t n_points, cons
     // hypotheses, their scores, the winners
     std::vector<int32_t> winner(P);
     std::vector<double> E((size_t)P * 9), Etry((size_t)P * 9);
+    P2S_TRY(block.time_begin());
     if (ctx) {
-        P2S_TRY(st.time_begin());
         hipLaunchKernelGGL(rp_hyp_kernel, dim3((unsigned)((PH + HYP_LANES - 1) / HYP_LANES)), dim3(HYP_LANES), 0, ctx->stream, a);
         hipLaunchKernelGGL(rp_score_kernel, dim3((unsigned)h_blocks, (unsigned)chunks, (unsigned)P), dim3(TILE), 0, ctx->stream, a);
         hipLaunchKernelGGL(rp_winner_kernel, dim3((unsigned)P), dim3(TILE), 0, ctx->stream, a);
         HIP_TRY(hipGetLastError());
-        P2S_TRY(st.down(winner.data(), a.winner, (size_t)P * 4));
-        P2S_TRY(st.down(E.data(), a.winE, (size_t)P * 72));
-        P2S_TRY(st.down(hyp_E, a.hypE, PH * 72));
-        P2S_TRY(st.down(hyp_cost, a.hyp_cost, PH * 8));
-        P2S_TRY(st.down(hyp_inliers, a.hyp_inl, PH * 4));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
     } else {
         std::vector<double> work(NWORK);
         for (int p = 0; p < P; ++p) {
@@ -756,12 +675,16 @@ int p2s_relative_poses_host(p2s_ctx *ctx, int32_t n_cams, int64_t n_points, cons
                     at = h;
                 }
             }
-            winner[p] = std::isfinite(best) ? at : -1;
+            a.winner[p] = std::isfinite(best) ? at : -1;
+            for (int i = 0; i < 9; ++i) a.winE[p * 9 + i] = a.winner[p] >= 0 ? a.hypE[((size_t)p * H + a.winner[p]) * 9 + i] : rp_nan();
         }
-        if (hyp_E) memcpy(hyp_E, a.hypE, PH * 72);
-        if (hyp_cost) memcpy(hyp_cost, a.hyp_cost, PH * 8);
-        if (hyp_inliers) memcpy(hyp_inliers, a.hyp_inl, PH * 4);
     }
+    P2S_TRY(block.get(winner.data(), a.winner, (size_t)P * 4));
+    P2S_TRY(block.get(E.data(), a.winE, (size_t)P * 72));
+    P2S_TRY(block.get(hyp_E, a.hypE, PH * 72));
+    P2S_TRY(block.get(hyp_cost, a.hyp_cost, PH * 8));
+    P2S_TRY(block.get(hyp_inliers, a.hyp_inl, PH * 4));
+    P2S_TRY(block.wait());
     a.tiles = (int32_t)((N + TILE - 1) / TILE);
 
     // the winners over every mutual point, then the refits
@@ -771,13 +694,14 @@ int p2s_relative_poses_host(p2s_ctx *ctx, int32_t n_cams, int64_t n_points, cons
     for (int p = 0; p < P; ++p) {
         if (mutual[p] < m) winner[p] = -1;
         valid[p] = active[p] = winner[p] >= 0;
-        for (int i = 0; i < 9; ++i) E[(size_t)p * 9 + i] = valid[p] ? (ctx ? E[(size_t)p * 9 + i] : a.hypE[((size_t)p * H + winner[p]) * 9 + i]) : rp_nan();
+        if (!valid[p])
+            for (int i = 0; i < 9; ++i) E[(size_t)p * 9 + i] = rp_nan();
     }
     double *dE = (double *)(blk + o_E);
     uint8_t *dact = (uint8_t *)(blk + o_act);
-    P2S_TRY(run.put(dE, E.data(), (size_t)P * 72));
-    P2S_TRY(run.put(dact, active.data(), P));
-    P2S_TRY(run.sums<NSTAT>(rp_stat_kernel, rp_stat_point, active, stat));
+    P2S_TRY(block.put_wait(dE, E.data(), (size_t)P * 72));
+    P2S_TRY(block.put_wait(dact, active.data(), P));
+    P2S_TRY((run.sums<NSTAT, RpStat>(active, stat)));
     for (int p = 0; p < P; ++p)
         if (valid[p]) cost[p] = stat[(size_t)p * NSTAT];
     std::vector<double> work(NWORK);
@@ -798,9 +722,9 @@ int p2s_relative_poses_host(p2s_ctx *ctx, int32_t n_cams, int64_t n_points, cons
             any = true;
         }
         if (!any) break;
-        P2S_TRY(run.put(dact, active.data(), P));
-        P2S_TRY(run.put(blk + o_nrm, nrm.data(), (size_t)P * 48));
-        P2S_TRY(run.sums<NSYM>(rp_normal_kernel, rp_normal_point, active, normal));
+        P2S_TRY(block.put_wait(dact, active.data(), P));
+        P2S_TRY(block.put_wait(blk + o_nrm, nrm.data(), (size_t)P * 48));
+        P2S_TRY((run.sums<NSYM, RpNormal>(active, normal)));
         Etry = E;
         for (int p = 0; p < P; ++p) {
             if (!active[p]) continue;
@@ -813,9 +737,9 @@ int p2s_relative_poses_host(p2s_ctx *ctx, int32_t n_cams, int64_t n_points, cons
                 memcpy(&Etry[(size_t)p * 9], &E[(size_t)p * 9], 72);
             }
         }
-        P2S_TRY(run.put(dact, active.data(), P));
-        P2S_TRY(run.put(dE, Etry.data(), (size_t)P * 72));
-        P2S_TRY(run.sums<NSTAT>(rp_stat_kernel, rp_stat_point, active, stat_try));
+        P2S_TRY(block.put_wait(dact, active.data(), P));
+        P2S_TRY(block.put_wait(dE, Etry.data(), (size_t)P * 72));
+        P2S_TRY((run.sums<NSTAT, RpStat>(active, stat_try)));
         for (int p = 0; p < P; ++p) {
             if (!active[p]) continue;
             if (stat_try[(size_t)p * NSTAT] < cost[p]) {
@@ -833,26 +757,27 @@ int p2s_relative_poses_host(p2s_ctx *ctx, int32_t n_cams, int64_t n_points, cons
     std::vector<double> cand((size_t)P * 48, 0.0);
     for (int p = 0; p < P; ++p)
         if (valid[p]) rp_decompose(&E[(size_t)p * 9], &cand[(size_t)p * 48]);
-    std::vector<uint32_t> front((size_t)P * 4, 0);
-    P2S_TRY(run.put(dact, valid.data(), P));
-    P2S_TRY(run.put(dE, E.data(), (size_t)P * 72));
-    P2S_TRY(run.put(blk + o_cand, cand.data(), cand.size() * 8));
+    std::vector<uint32_t> front((size_t)P * 4);
+    P2S_TRY(block.put_wait(dact, valid.data(), P));
+    P2S_TRY(block.put_wait(dE, E.data(), (size_t)P * 72));
+    P2S_TRY(block.put_wait(blk + o_cand, cand.data(), cand.size() * 8));
     if (ctx) {
         HIP_TRY(hipMemsetAsync(a.front, 0, (size_t)P * 16, ctx->stream));
         hipLaunchKernelGGL(rp_front_kernel, dim3((unsigned)a.tiles, (unsigned)P), dim3(TILE), 0, ctx->stream, a);
         HIP_TRY(hipGetLastError());
-        P2S_TRY(st.time_end());
-        P2S_TRY(st.down(front.data(), a.front, (size_t)P * 16));
-        P2S_TRY(st.down(mask_out, a.mask, (size_t)P * N));
-        P2S_TRY(st.finish(P2S_TIMED_RELPOSE));
     } else {
+        memset(a.front, 0, (size_t)P * 16);
         for (int p = 0; p < P; ++p)
             for (int64_t n = 0; n < N; ++n) {
                 const int bits = rp_front_point(a, p, n);
-                mask_out[(size_t)p * N + n] = (uint8_t)(bits >> 4);
-                for (int i = 0; i < 4; ++i) front[(size_t)p * 4 + i] += bits >> i & 1;
+                a.mask[(size_t)p * N + n] = (uint8_t)(bits >> 4);
+                for (int i = 0; i < 4; ++i) a.front[p * 4 + i] += bits >> i & 1;
             }
     }
+    P2S_TRY(block.time_end());
+    P2S_TRY(block.get(front.data(), a.front, (size_t)P * 16));
+    P2S_TRY(block.get(mask_out, a.mask, (size_t)P * N));
+    P2S_TRY(block.finish(P2S_TIMED_RELPOSE));
     for (int p = 0; p < P; ++p) {
         int best = 0;
         for (int i = 1; i < 4; ++i)

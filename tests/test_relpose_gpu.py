@@ -90,10 +90,12 @@ def compare_results(got, ref, tag, clear=None):
 
 
 # N around the 64 lanes of a wave and the 256 points of a pass; 257 and 700 are past a single chunk (2 cameras: the points
-# are cut into chunks of a pass each); H around a wave and the 256 hypotheses of a workgroup; every sample size's ends
+# are cut into chunks of a pass each); H around a wave and the 256 hypotheses of a workgroup; every sample size's ends;
+# 32 cameras at 1025 points: the per-point passes take 3 parts over 5 tiles (2, 2 and 1 of them), and the refits leave
+# pairs out of a pass and keep others in (0, 1, 2 and 3 refits kept)
 SHAPES = [(2, 8, 64, 8, 1), (2, 63, 64, 8, 2), (2, 64, 64, 8, 3), (2, 65, 64, 8, 4), (2, 257, 64, 8, 5), (2, 700, 64, 8, 6),
           (2, 65, 1, 8, 7), (2, 65, 63, 8, 8), (2, 65, 65, 8, 9), (2, 65, 257, 8, 10), (2, 130, 64, 12, 11), (2, 130, 64, 16, 12),
-          (3, 65, 64, 8, 13), (32, 40, 8, 8, 14)]
+          (3, 65, 64, 8, 13), (32, 40, 8, 8, 14), (32, 1025, 8, 8, 15)]
 
 
 @pytest.mark.parametrize('Cn, N, H, m, seed', SHAPES)
@@ -159,6 +161,10 @@ def test_two_calls_return_the_same_bytes(eng, ring4):
         assert a[k].tobytes() == b[k].tobytes(), k
     xn2, us2, pairs2, smp2, thr22 = sliced(2, 700, 257, 8, 6)                       # chunks of points, two workgroups of hypotheses
     a, b = (eng.relative_poses(xn2, us2, pairs2, smp2, thr22, all_hypotheses=True) for _ in range(2))
+    for k in a:
+        assert a[k].tobytes() == b[k].tobytes(), k
+    xn3, us3, pairs3, smp3, thr23 = sliced(32, 1025, 8, 8, 15)                      # more tiles than parts, an uneven last part
+    a, b = (eng.relative_poses(xn3, us3, pairs3, smp3, thr23, all_hypotheses=True) for _ in range(2))
     for k in a:
         assert a[k].tobytes() == b[k].tobytes(), k
 

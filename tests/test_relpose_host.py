@@ -12,6 +12,7 @@ import relpose_numpy as rn
 import rigs
 from pose2sim_amd import _lib, engine
 from pose2sim_amd import calib_from_keypoints as cfk
+from test_relpose_gpu import compare_hypotheses, compare_results, sliced
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -71,6 +72,21 @@ def test_mirror_and_host_path_against_the_truth(family, Cn, noise, p_out, H, c_m
     dcost = (np.abs(got['cost'] - ref['cost']) / ref['cost']).max()
     print(f'    host path against the mirror: E {dE:.2e}, R {dR:.2e}, t {dt:.2e}, cost {dcost:.2e} relative')
     assert dE <= rn.WIN_E_BOUND and dR <= rn.RT_BOUND and dt <= rn.RT_BOUND and dcost <= rn.RESULT_COST_REL_BOUND
+
+
+@pytest.mark.parametrize('Cn, N, H, m, seed', [(32, 1025, 8, 8, 15)])
+def test_host_path_passes_of_more_tiles_than_parts(Cn, N, H, m, seed):
+    """496 pairs at 1025 points: the per-point passes take 3 parts over 5 tiles (2, 2 and 1 of them); the refits leave pairs
+    out of a pass and keep others in."""
+    xn, us, pairs, smp, thr2 = sliced(Cn, N, H, m, seed)
+    ref = rn.relative_poses(xn, us, pairs, smp, thr2)
+    got = engine.relative_poses_host(xn, us, pairs, smp, thr2, all_hypotheses=True)
+    assert -(-N // _lib.P2S_RELPOSE_TILE) == 5 and len(pairs) == 496
+    assert rn.winners_are_clear(ref) and (ref['winner'] >= 0).all()
+    assert np.bincount(ref['refits'], minlength=4).min() > 0                  # pairs with 0, 1, 2 and 3 refits kept
+    tag = f'host path, C {Cn} (P {len(pairs)}), N {N}, H {H}, m {m}'
+    compare_hypotheses(got, ref, xn, us, pairs, thr2, tag)
+    compare_results(got, ref, tag)
 
 
 def test_host_path_every_hypothesis_and_its_own_refusals():
