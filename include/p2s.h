@@ -610,6 +610,11 @@ int p2s_get_assoc_stats(p2s_ctx *ctx, uint64_t *out, int32_t reset);
  *                         P2S_ASSOC_FORM_GENERAL: the general kernel (no symmetry assumed) at every size
  *   P2S_TUNE_GAPS_WORKSPACE_KB  cap (KiB, default P2S_GAPS_WORKSPACE_KB) of the spline kinds' workspace in
  *                         p2s_interpolate_gaps: the columns go through it in chunks that fit, one column at least
+ *   P2S_TUNE_POISON_STAGING  -1 (default): off; 0..255: every buffer the context owns -- the staging slots of the *_host
+ *                         calls and the work-list triangulation's list, counters and deep-level buffers -- is filled with
+ *                         this byte over its whole capacity, on the context's stream, before the call that asked for it
+ *                         uses it.  What a call finds in such a buffer is garbage by contract; this makes it the same
+ *                         hostile garbage every time (0xFF: NaN, -1 and set flags) for tests/test_engine_reuse_gpu.py
  *   P2S_TUNE_DIAG_MODE    kernel diagnostics of a -DP2S_DIAG build (exp/README.md); refused by the shipped library */
 #define P2S_TUNE_TRI_PATH 1
 #define P2S_TUNE_FORCE_TILED 2
@@ -624,6 +629,7 @@ int p2s_get_assoc_stats(p2s_ctx *ctx, uint64_t *out, int32_t reset);
 #define P2S_TUNE_SCREEN 11
 #define P2S_TUNE_POOL_TILES 12
 #define P2S_TUNE_GAPS_WORKSPACE_KB 13
+#define P2S_TUNE_POISON_STAGING 14
 #define P2S_ASSOC_FORM_AUTO 0
 #define P2S_ASSOC_FORM_GENERAL 1
 #define P2S_TRI_PATH_AUTO 0

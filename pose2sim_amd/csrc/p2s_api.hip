@@ -275,6 +275,10 @@ int p2s_set_tuning(p2s_ctx *ctx, int32_t key, int32_t value) {
         if (value < 1) return p2s_set_error(P2S_ERR_INVALID_ARG, "workspace cap must be >= 1 KiB");
         ctx->gaps_ws_kb = value;
         return P2S_OK;
+    case P2S_TUNE_POISON_STAGING:
+        if (value < -1 || value > 255) return p2s_set_error(P2S_ERR_INVALID_ARG, "poison byte %d outside -1 (off), 0 .. 255", value);
+        ctx->poison = value;
+        return P2S_OK;
     case P2S_TUNE_ASSOC_FORM:
         if (value != P2S_ASSOC_FORM_AUTO && value != P2S_ASSOC_FORM_GENERAL)
             return p2s_set_error(P2S_ERR_INVALID_ARG, "unknown association kernel form %d", value);

@@ -88,10 +88,22 @@ struct p2s_ctx {
     int screen = 1;                                  // p2s_tri_pool.hip: fp32 screen of the camera-subset candidates
     int gaps_ws_kb = P2S_GAPS_WORKSPACE_KB;          // p2s_gaps.hip: cap of the spline kinds' workspace
     int pool_tiles = 5;                              // p2s_tri_pool.hip: tiles a wave streams before it searches their pooled failures (2..6)
+    int poison = -1;                                 // 0..255: p2s_poison fills every context-owned buffer with this byte before a call uses it
 };
 
+// P2S_TUNE_POISON_STAGING (tests only).  What an earlier call left in a staging slot or in one of the six role buffers of
+// the work-list triangulation (wl_rec, wl_count, deep_entries / ctl / sched / partials) is garbage by contract; with the
+// switch on, that garbage is this byte over the buffer's whole capacity, put there on ctx->stream before anything of the
+// call that asked for the buffer.  No buffer is exempt: none of them holds content meant to outlive a call.  Off is one
+// branch.
+inline int p2s_poison(p2s_ctx *ctx, const Scratch &s) {
+    if (ctx->poison >= 0 && s.p) HIP_TRY(hipMemsetAsync(s.p, ctx->poison, s.bytes, ctx->stream));
+    return P2S_OK;
+}
+
 // Device buffers of one *_host call.  The i-th buffer the call asks for is ctx->slot[i]: two pointers of one call never
-// share a slot, a slot only grows (hipFree / hipMalloc on growth alone), and what an earlier call left in it is garbage.
+// share a slot, a slot only grows (hipFree / hipMalloc on growth alone), and what an earlier call left in it is garbage
+// (p2s_poison, above, makes it the same garbage every time for the tests).
 // A buffer is never NULL (at least 16 bytes); copies of 0 bytes and downloads to a NULL host pointer are skipped.
 struct Stage {
     p2s_ctx *ctx;
@@ -100,6 +112,7 @@ struct Stage {
         if (used == P2S_N_SLOTS) return p2s_set_error(P2S_ERR_INVALID_ARG, "more than %d staging buffers in one call", P2S_N_SLOTS);
         Scratch &s = ctx->slot[used++];
         P2S_TRY(s.ensure(bytes > 16 ? bytes : 16));
+        P2S_TRY(p2s_poison(ctx, s));
         d = (T *)s.p;
         return P2S_OK;
     }

@@ -1184,6 +1184,8 @@ static int tri_work_list(p2s_ctx *ctx, int64_t n_blocks, int32_t n_kpts, int32_t
     const size_t list_bytes = (size_t)P2S_WL_SHARDS * shard_cap * rec_bytes;
     P2S_TRY(ctx->wl_rec.ensure(2 * list_bytes));
     P2S_TRY(ctx->wl_count.ensure((size_t)n_chunks * 2 * P2S_WL_SHARDS * sizeof(uint32_t)));
+    P2S_TRY(p2s_poison(ctx, ctx->wl_rec));        // on ctx->stream: the search kernels on side_stream wait for ev_k1, recorded after it
+    P2S_TRY(p2s_poison(ctx, ctx->wl_count));
     HIP_TRY(hipMemsetAsync(ctx->wl_count.p, 0, (size_t)n_chunks * 2 * P2S_WL_SHARDS * sizeof(uint32_t), ctx->stream));
 
     // search kernel geometry: LDS = [P][binom][waves x 64 records]
@@ -1238,6 +1240,7 @@ static int tri_work_list(p2s_ctx *ctx, int64_t n_blocks, int32_t n_kpts, int32_t
         P2S_TRY(ctx->deep_ctl.ensure(64));
         P2S_TRY(ctx->deep_sched.ensure((size_t)kDeepTickets * 2 * sizeof(uint32_t)));
         P2S_TRY(ctx->deep_partials.ensure((size_t)kDeepTickets * sizeof(P2sDeepPartial)));
+        for (const Scratch *s : {&ctx->deep_entries, &ctx->deep_ctl, &ctx->deep_sched, &ctx->deep_partials}) P2S_TRY(p2s_poison(ctx, *s));
         dargs.prune = ctx->deep_prune ? 1u : 0u;
         dargs.entries = (unsigned char *)ctx->deep_entries.p;
         dargs.ctl = (uint32_t *)ctx->deep_ctl.p;

@@ -182,6 +182,9 @@ def _track_persons(lib, handle, Q, first_frame, max_dist, state):
     if rc == _lib.P2S_ERR_INVALID_ARG:
         raise TrackShapeError(f'p2s error {rc}: {lib.p2s_last_error().decode()}')
     _lib.check(rc)
+    for t in np.flatnonzero(status[:, 0] > 0):                        # a stopped trial: the library writes nothing from that frame on
+        stop = slice(off[t] + status[t, 0] - 1, off[t + 1])
+        rows[stop], ids[stop], dist[stop], n_slots[stop] = np.nan, -1, np.nan, 0
     cut = lambda a: [a[off[t]:off[t + 1]] for t in range(T)]         # noqa: E731
     out = (cut(rows), cut(ids), cut(dist), cut(n_slots), [state_out[t, :n_out[t]] for t in range(T)], list(status))
     return tuple(o[0] for o in out) if single else out
@@ -424,6 +427,7 @@ class Engine:
     # p2s_set_tuning keys (include/p2s.h): experiments and tests only, results never depend on them
     TUNE_TRI_PATH, TUNE_FORCE_TILED, TUNE_NO_OVERLAP, TUNE_SEARCH_JOB, TUNE_DIAG_MODE, TUNE_MAX_SUBSETS, TUNE_DEEP_MIN_SUBSETS = 1, 2, 3, 4, 5, 6, 7
     TUNE_ASSOC_FORM, TUNE_POOL_SINGLES_PCT, TUNE_DEEP_PRUNE, TUNE_SCREEN, TUNE_POOL_TILES, TUNE_GAPS_WORKSPACE_KB = 8, 9, 10, 11, 12, 13
+    TUNE_POISON_STAGING = 14
     TRI_PATH_AUTO, TRI_PATH_WORKLIST, TRI_PATH_ONE_TILE, TRI_PATH_POOLED, TRI_PATH_TWO_TILES = 0, 1, 2, 3, 4
     ASSOC_FORM_AUTO, ASSOC_FORM_GENERAL = 0, 1
 
@@ -1009,8 +1013,8 @@ class Engine:
         workgroup of one launch (csrc/p2s_track.hip).  -> (Q_rows [F][P][K][3] the points in tracked order, ids [F][P] int32
         the detection every slot took or -1, matched_dist [F][P] the mean keypoint distance of every kept pair or NaN,
         n_slots [F] int32, state [n][K][3], status [2] int32: zeros, or (the first frame, plus 1, that would have passed 32
-        slots, the assignment's refusal if that stopped it) -- nothing from that frame on is defined), each a list for a
-        list of trials.  A shape the kernel does not take raises TrackShapeError."""
+        slots, the assignment's refusal if that stopped it) -- from that frame on the library writes nothing, and the rows are NaN, the
+        ids -1, matched_dist NaN and n_slots 0), each a list for a list of trials.  A shape the kernel does not take raises TrackShapeError."""
         return _track_persons(self._lib, self._h, Q, first_frame, max_dist, state)
 
     def track_persons_3d_device(self, frame_off, first_frame, P, K, d_Q, max_dist=None, d_state_in=None, d_n_state_in=None, d_ids=None,

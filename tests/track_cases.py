@@ -110,7 +110,10 @@ def check_overflow(run):
     got = run(Q, first_frame=0, max_dist=max_dist)
     assert list(got[5]) == [first_over + 1, 0]
     assert_same_run(got, want, upto=first_over, what='overflow')
-    short = tn.replay(Q[:first_over], 0, max_dist)
+    # from the frame that stopped the trial on the library writes nothing: the engine returns "nobody", not what came down
+    assert np.isnan(got[0][first_over:]).all() and (got[1][first_over:] == -1).all() and np.isnan(got[2][first_over:]).all()
+    assert not got[3][first_over:].any() and len(got[0]) == len(Q)
+    short =tn.replay(Q[:first_over], 0, max_dist)
     assert short[3][-1] == 32
     got = run(Q[:first_over], first_frame=0, max_dist=max_dist)
     assert not got[5].any() and len(got[4]) == 32
