@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI in include/p2s.h (csrc/libp2s_hip.so).
+"""ctypes binding of the C-ABI in include/p2s.h and include/p2s_floor.h (csrc/libp2s_hip.so).
 
 The library is the only compute path: there is no CPU fallback.  ``load()`` raises if the shared
 object is missing; ``Context()`` raises if no MI355X is visible.
@@ -40,6 +40,7 @@ P2S_MEASURE_ALL_SLOW, P2S_MEASURE_FEW_SMALL_ANGLES, P2S_MEASURE_ALL_DATA = 1, 2,
 P2S_REFINE_TILE, P2S_REFINE_MAX_PARTS = 256, 128   # csrc/p2s_refine.hip: points a workgroup pass, partial sums a launch
 P2S_RELPOSE_TILE, P2S_RELPOSE_MAX_CHUNKS, P2S_RELPOSE_MAX_PARTS = 256, 64, 128   # csrc/p2s_relpose.hip: points a pass, chunk sums, partial sums
 P2S_RELPOSE_MIN_SAMPLE, P2S_RELPOSE_MAX_SAMPLE = 8, 16
+P2S_FLOOR_TILE, P2S_FLOOR_MAX_CHUNKS, P2S_FLOOR_MAX_PARTS = 256, 64, 128   # csrc/p2s_floor.hip: points a pass, chunk sums, partial sums
 P2S_MEASURE_ROLES =('RShoulder', 'LShoulder', 'RHip', 'LHip', 'Hip', 'Neck', 'RKnee', 'LKnee', 'RAnkle', 'LAnkle')
 
 
@@ -200,6 +201,13 @@ SIGNATURES = {
                                    C.POINTER(C.c_int32)]),
 }
 
+# the same for include/p2s_floor.h, the floor stage's header
+FLOOR_SIGNATURES = {
+    'p2s_fit_planes_host': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+                            + [C.c_void_p] * 12),
+    'p2s_floor_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+}
+
 # entry points a library built before them lacks (P2S_LIB may name one): left unbound, and the feature is refused
 OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_host', 'p2s_json_gather_largest_person',
             'p2s_copy_files', 'p2s_reproject_host', 'p2s_reproject_kernel_ms', 'p2s_write_openpose_files',
@@ -212,7 +220,7 @@ OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_h
             'p2s_track_persons_device', 'p2s_track_persons_kernel_ms', 'p2s_interpolate_gaps', 'p2s_fill_gaps', 'p2s_gap_runs',
             'p2s_gaps_kernel_ms', 'p2s_timeline_rows_host', 'p2s_timeline_kernel_ms', 'p2s_timeline_write_csv',
             'p2s_refine_extrinsics_host', 'p2s_refine_kernel_ms', 'p2s_refine_held_coord', 'p2s_relative_poses_host',
-            'p2s_relpose_kernel_ms'}
+            'p2s_relpose_kernel_ms', 'p2s_fit_planes_host', 'p2s_floor_kernel_ms'}
 
 _lib = None
 
@@ -230,7 +238,7 @@ def load():
         raise P2sError(f'{LIB_PATH} is missing: run `python -c "import __graft_entry__ as g; g.build()"` '
                        '(hipcc --offload-arch=gfx950). There is no CPU fallback.')
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **FLOOR_SIGNATURES}.items():
         if name in OPTIONAL and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

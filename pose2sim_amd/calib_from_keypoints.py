@@ -9,12 +9,13 @@ assembled along a maximum spanning tree of their inlier counts, and the result s
 
 What the data must be: ONE person who MOVES THROUGH the volume.  A person who stays within a few decimetres gives a point
 cloud that is flat as seen from 5 m, the two-view geometry is then close to weak perspective, and no pair is recovered.
-The world frame of the result is camera 0's (R = I, t = 0); it is not aligned to the floor.  The scale comes from a known
-baseline, from the person's height, or is arbitrary (first baseline = 1).  cv2.findEssentialMat has never run next to this
+The world frame of the result is camera 0's (R = I, t = 0); with floor = True (--floor) it is put on the floor the person walks
+on instead, Z up and Y along the walk (calib_align_floor), which needs a scale in metres and is refused without one.  The scale comes from
+a known baseline, from the person's height, or is arbitrary (first baseline = 1).  cv2.findEssentialMat has never run next to this
 code and nothing here is pinned to it.
 
     python -m pose2sim_amd.calib_from_keypoints -c Intrinsics.toml -p pose [-o Calib.toml] [--baseline cam01 cam02 2.5 |
-                                                --height 1.75] [--threshold 4] [--hypotheses 4096] [--sample-size 8] [--seed 0]
+                                                --height 1.75] [--floor [--floor-threshold 0.03] [--floor-hypotheses 1024]] [--threshold 4] [--hypotheses 4096] [--sample-size 8] [--seed 0]
                                                 [--likelihood 0.3] [--huber 3] [--keypoints Nose,Neck,...] [--pose-model HALPE_26]
 """
 import argparse
@@ -183,16 +184,21 @@ def rescaled(cams, s):
 
 def calibrate_from_keypoints(calib_toml, pose_dir, out_toml=None, baseline=None, height=None, keypoints=None, frame_range=None,
                              pose_model='HALPE_26', lik_thr=0.3, thr_px=4.0, hypotheses=4096, sample_size=8, score_points=16384, seed=0,
-                             huber_px=3.0, min_cams=2, max_iter=100, ftol=1e-12, min_inliers=30, engine=None):
+                             huber_px=3.0, min_cams=2, max_iter=100, ftol=1e-12, min_inliers=30, engine=None, floor=False, floor_threshold=0.03,
+                             floor_hypotheses=1024, ankle_height=0.08):
     """Extrinsics of the cameras of calib_toml (its intrinsics and lenses are kept, its extrinsics ignored) from the keypoints
     under pose_dir, written in the reference's schema with adjusted = true to out_toml (default: <calib_toml>_keypoints.toml).
     calib_toml may be the dict of calib.retrieve_calib_params and pose_dir an array xyl [F..., C, K, 3]: nothing is written
     without an out_toml then.  Scale: baseline = (camera name a, camera name b, metres), or height = the person's, in metres
     (measurements.compute_height on the triangulated trial; needs the keypoints of pose_model), or neither: the first tree
-    edge's baseline is 1 and a warning says so.  -> (out_toml or None, cams, report of the last refinement with the tree's 'edges', the assembled 'start' and its 'rms_start')."""
+    edge's baseline is 1 and a warning says so.  floor = True puts the world on the floor under the person's feet after the scale
+    step (calib_align_floor.floor_frame on the triangulated trial with floor_threshold (m), floor_hypotheses and ankle_height; the
+    report gains 'floor'); it needs a baseline or a height, since an arbitrary scale has no metres, and is refused without.  -> (out_toml or None, cams, report of the last refinement with the tree's 'edges', the assembled 'start' and its 'rms_start')."""
     from .engine import Engine
     if baseline is not None and height is not None:
         raise ValueError('give a baseline or a height, not both')
+    if floor and baseline is None and height is None:
+        raise ValueError('floor = True needs a baseline or a height: the floor is looked for with a threshold in metres')
     from_file = not isinstance(calib_toml, dict)
     cams = calib.retrieve_calib_params(calib_toml) if from_file else calib_toml
     ids, kp_names = calib_refine.select_keypoints(pose_model, keypoints)
@@ -238,6 +244,12 @@ def calibrate_from_keypoints(calib_toml, pose_dir, out_toml=None, baseline=None,
     else:
         logging.warning('No baseline and no height given: the scale of the calibration is arbitrary (the first baseline is 1).')
     report = dict(report, edges=info['edges'], rms_start=rms_start, start=start)
+    if floor:
+        from . import calib_align_floor
+        A, b, report['floor'] = calib_align_floor.floor_frame(calib_align_floor.triangulated(refined, xyl, lik_thr, min_cams, eng), kp_names,
+                                                              hypotheses=floor_hypotheses, threshold=floor_threshold, seed=seed,
+                                                              ankle_height=ankle_height, engine=eng)
+        refined = calib_align_floor.moved_cameras(refined, A, b)
     logging.info(f'Extrinsics from {report["kept_points"]} points, cost {report["cost_after"]:.6g}.')
     for c, name in enumerate(names):
         logging.info(f'  {name}: weighted RMS reprojection error {rms_start[c]:.3f} px at the assembled start -> {report["rms_after"][c]:.3f} px')
@@ -258,6 +270,10 @@ def parse_args(argv=None):
     parser.add_argument('-o', '--output', default=None, help='calibration to write (default: <calib>_keypoints.toml)')
     parser.add_argument('--baseline', nargs=3, default=None, metavar=('A', 'B', 'M'), help='cameras A and B are M metres apart')
     parser.add_argument('--height', type=float, default=None, help="the person's height, m")
+    parser.add_argument('--floor', action='store_true', help='put the world frame on the floor the person walks on: Z up, Y along the walk (needs --baseline or --height)')
+    parser.add_argument('--floor-threshold', type=float, default=0.03, help='--floor: inlier distance from the floor, m')
+    parser.add_argument('--floor-hypotheses', type=int, default=1024, help='--floor: triples of foot points that are tried')
+    parser.add_argument('--ankle-height', type=float, default=0.08, help='--floor: height of the ankles over the floor, m (models without heels and toes)')
     parser.add_argument('--threshold', type=float, default=4.0, help='inlier threshold of the Sampson distance, px')
     parser.add_argument('--hypotheses', type=int, default=4096, help='hypotheses a camera pair')
     parser.add_argument('--sample-size', type=int, default=8, help='correspondences a hypothesis (8 .. 16)')
@@ -283,6 +299,10 @@ def parse_args(argv=None):
             parser.error('--baseline takes two camera names and a length in metres')
         if not args.baseline[2] > 0 or args.baseline[0] == args.baseline[1]:
             parser.error('--baseline needs two different cameras and a positive length')
+    if args.floor and args.baseline is None and args.height is None:
+        parser.error('--floor needs --baseline or --height: the floor is looked for with a threshold in metres')
+    if not args.floor_threshold > 0 or args.floor_hypotheses < 1 or args.ankle_height < 0:
+        parser.error('--floor-threshold must be positive, --floor-hypotheses 1 or more, --ankle-height 0 or more')
     if args.height is not None and not args.height > 0:
         parser.error('--height must be positive')
     if not args.threshold > 0 or not args.huber > 0:
@@ -298,7 +318,8 @@ def main(argv=None):
     calibrate_from_keypoints(args.calib, args.pose, args.output, baseline=args.baseline, height=args.height, keypoints=args.keypoints,
                              frame_range=args.frames, pose_model=args.pose_model, lik_thr=args.likelihood, thr_px=args.threshold,
                              hypotheses=args.hypotheses, sample_size=args.sample_size, score_points=args.score_points, seed=args.seed,
-                             huber_px=args.huber, min_cams=args.min_cams)
+                             huber_px=args.huber, min_cams=args.min_cams, floor=args.floor, floor_threshold=args.floor_threshold,
+                             floor_hypotheses=args.floor_hypotheses, ankle_height=args.ankle_height)
 
 
 if __name__ == '__main__':

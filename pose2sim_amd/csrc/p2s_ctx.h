@@ -52,7 +52,7 @@ struct Scratch {
 // The stages that time their own kernels: one slot of p2s_ctx::kernel_ms each.
 enum { P2S_TIMED_REPROJ, P2S_TIMED_JITTER, P2S_TIMED_CONFIDENCE, P2S_TIMED_ID_SWITCH, P2S_TIMED_GAIT, P2S_TIMED_MEASURE,
        P2S_TIMED_TRACK_SELECT, P2S_TIMED_TRACK_PERSONS, P2S_TIMED_GAPS, P2S_TIMED_TIMELINE, P2S_TIMED_REFINE, P2S_TIMED_RELPOSE,
-       P2S_N_TIMED };
+       P2S_TIMED_FLOOR, P2S_N_TIMED };
 
 struct p2s_ctx {
     int device = 0;
@@ -65,7 +65,7 @@ struct p2s_ctx {
     bool full_calib = false;     // K, dist, R, T, newK were provided
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_stage[2] = {nullptr, nullptr};     // around the kernels of the *_host call that times itself
-    float kernel_ms[P2S_N_TIMED] = {-1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f};   // the last call's kernel time of every P2S_TIMED_* stage; -1: has not run
+    float kernel_ms[P2S_N_TIMED] = {-1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f};   // the last call's kernel time of every P2S_TIMED_* stage; -1: has not run
     hipStream_t side_stream = nullptr;               // search kernels run here, beside the next chunk's streaming pass
     hipEvent_t ev_k1[2] = {nullptr, nullptr}, ev_k2[2] = {nullptr, nullptr};
     Scratch slot[P2S_N_SLOTS];                       // staging of the *_host calls (Stage): no role, no owner between calls

@@ -381,6 +381,40 @@ def relative_poses_host(xn, usable, pairs, samples, thr2, rounds=3, all_hypothes
     return _relative_poses(_lib.load(), None, xn, usable, pairs, samples, thr2, rounds, all_hypotheses, score_points)
 
 
+def _fit_planes(lib, handle, points, usable, ref, samples, thr, rounds, all_hypotheses):
+    fn = _entry(lib, 'p2s_fit_planes_host')
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    if points.ndim != 3 or points.shape[-1] != 3:
+        raise P2sError(f'points has shape {points.shape}; expected [B][N][3]')
+    B, N = points.shape[:2]
+    usable = np.ascontiguousarray(np.asarray(usable) != 0, dtype=np.uint8)
+    ref = np.ascontiguousarray(ref, dtype=np.float64)
+    samples = np.ascontiguousarray(samples, dtype=np.int32)
+    thr = _per(thr, B)
+    if usable.shape != (B, N):
+        raise P2sError(f'usable has shape {usable.shape}; expected {(B, N)}')
+    if ref.shape != (B, 3):
+        raise P2sError(f'ref has shape {ref.shape}; expected {(B, 3)}')
+    if samples.ndim != 3 or samples.shape[0] != B or samples.shape[2] != 3:
+        raise P2sError(f'samples has shape {samples.shape}; expected [{B}][H][3]')
+    H = samples.shape[1]
+    out = {'plane': np.empty((B, 4)), 'cost': np.empty(B), 'inliers': np.empty(B, dtype=np.int32), 'below': np.empty(B, dtype=np.int32),
+           'winner': np.empty(B, dtype=np.int32), 'refits': np.empty(B, dtype=np.int32), 'centroid': np.empty((B, 3)), 'evals': np.empty((B, 3)),
+           'mask': np.empty((B, N), dtype=np.uint8)}
+    if all_hypotheses:
+        out.update(hyp_plane=np.empty((B, H, 4)), hyp_cost=np.empty((B, H)), hyp_inliers=np.empty((B, H), dtype=np.int32))
+    _lib.check(fn(handle, B, N, _ptr(points), _ptr(usable), _ptr(ref), H, _ptr(samples), _ptr(thr), int(rounds),
+                  *[_ptr(out[k]) for k in ('plane', 'cost', 'inliers', 'below', 'winner', 'refits', 'centroid', 'evals', 'mask')],
+                  *[_ptr(out.get(k)) for k in ('hyp_plane', 'hyp_cost', 'hyp_inliers')]))
+    out['mask'] = out['mask'].view(bool)
+    return out
+
+
+def fit_planes_host(points, usable, ref, samples, thr, rounds=3, all_hypotheses=False):
+    """Engine.fit_planes with the library's host path (no GPU): the same per-hypothesis and per-point functions."""
+    return _fit_planes(_lib.load(), None, points, usable, ref, samples, thr, rounds, all_hypotheses)
+
+
 class Engine:
     def __init__(self, device=0):
         self._lib = _lib.load()
@@ -1105,6 +1139,21 @@ class Engine:
         """Time of the last relative_poses() call between the HIP events around its kernels (the refits' eigen-solves on the
         host between them included)."""
         return _kernel_ms(self, 'relpose')
+
+    # -- the dominant plane of point sets: the floor under a walk (csrc/p2s_floor.hip, DESIGN.md 4.23) -----------------------------
+    def fit_planes(self, points, usable, ref, samples, thr, rounds=3, all_hypotheses=False):
+        """The plane n . x = d that most points of every problem lie on, by hypothesise and score.  points [B][N][3], usable
+        [B][N], ref [B][3] a point above the plane (it orients n), samples [B][H][3] point indices, thr the inlier distance in
+        the points' unit (one, or one a problem); at most `rounds` refits on the inliers, kept while the cost falls.
+        -> dict: plane [B][4] (n, d), cost, inliers, below, winner, refits [B], centroid [B][3] and evals [B][3] of the
+        inliers (ascending eigenvalues of their scatter over their count), mask [B][N]; with all_hypotheses also hyp_plane
+        [B][H][4], hyp_cost, hyp_inliers [B][H].  A problem without a result has NaN, counts 0 and winner -1."""
+        return _fit_planes(self._lib, self._h, points, usable, ref, samples, thr, rounds, all_hypotheses)
+
+    def floor_kernel_ms(self):
+        """Time of the last fit_planes() call between the HIP events around its kernels (the refits' eigen-solves on the host
+        between them included)."""
+        return _kernel_ms(self, 'floor')
 
     # -- synchronization (synchronization.py:1271-1343, 1541-1585) -------------------------------------------------------
     def sync_speeds(self, coords, b, a, zi):

@@ -145,6 +145,29 @@ def load_trc(trc_path):
     return block.iloc[:, 0].to_numpy(), block.iloc[:, 1].to_numpy(dtype=np.float64), coords, markers, header
 
 
+def units(header):
+    """The Units field of the header lines of load_trc (line 3, under the label of line 2); '' when there is none."""
+    labels, values = header[1].rstrip('\n').split('\t'), header[2].rstrip('\n').split('\t')
+    return values[labels.index('Units')].strip() if 'Units' in labels and labels.index('Units') < len(values) else ''
+
+
+def time_column(trc_path):
+    """The Time column as Python reads its digits (float() gives back the double that repr() wrote; load_trc's tokenizer may be
+    one unit in the last place off): what write_rows needs to write the same digits again."""
+    with open(trc_path, 'r') as fh:
+        return np.array([float(line.split('\t')[1]) for line in fh.read().split('\n')[5:] if line.strip()])
+
+
+def write_like(trc_path, header, frames, time_col, stored):
+    """A .trc file with the header lines of another (load_trc's; the file name of line 1 becomes trc_path's), these frame
+    numbers and times, and stored [F][3 K] coordinates in the file's own (Y-up) column order."""
+    first = header[0].rstrip('\n').split('\t')
+    first[-1] = os.path.basename(trc_path)
+    with open(trc_path, 'w') as fh:
+        fh.write('\t'.join(first) + '\n' + ''.join(header[1:]))
+    write_rows(trc_path, frames, time_col, stored)
+
+
 def read_trc(trc_path):
     """The reference's reader contract (common.py:149-175) -> (Q_coords, frames_col, time_col, markers, header): a
     DataFrame with every marker's name on its three columns, two Series, the marker names, the header lines."""
