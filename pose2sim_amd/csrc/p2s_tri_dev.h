@@ -123,8 +123,11 @@ __device__ __noinline__ double3 refine_eigvec(double n00, double m01, double m02
 // inhomogeneous least-squares point -- converges cubically; an iterate that jumps over the pole
 // mu_1 (M - lambda I no longer positive definite) is pulled back by bisection, so the SMALLEST
 // root is the one found.  The 3x3 systems go through the adjugate (one reciprocal).  The loop
-// stops on a first-order bound of the error of q and returns q + dlambda * dq/dlambda; agreement
-// with the SVD is ~1e-10 relative (tests/test_tri_gpu.py).
+// stops on a first-order bound of the error of q and returns q + dlambda * dq/dlambda.  Agreement
+// with the SVD is ~1e-10 relative on likelihoods of 0.3 .. 1 (tests/test_tri_gpu.py).  With weight
+// ratios of 1e-3 .. 1e-6 between the cameras of a unit it is what the normal equations allow: within
+// K e_cond of the exact point, e_cond = 2^-53 |N0| / (lambda_2 - lambda_1) (1 + |q|^2) for the level-0
+// matrix N0 (tests/tri_exact.py, tests/test_tri_exact_gpu.py; 7e-9 m at worst on its cases).
 // One evaluation of the secular function at lambda: q(lambda) = -(M - lambda)^-1 b through the adjugate, its
 // derivative p = dq/dlambda = (M - lambda)^-1 q, f = c - lambda + b.q and the Halley step of f (Newton's when the
 // Halley denominator is not positive).

@@ -19,8 +19,8 @@ stadium x pincushion, close x wide and four runaway cases whose observations lea
 `icdist < 0` exit.  Pinhole cases bring the work-list and one-launch paths to the eight geometries the pooled kernel passed.
 
 Every unit of every case (300 frames x HALPE_26 = 7.8 k) is compared with oracle/tri_oracle through test_tri_gpu._compare at
-its bars.  The likelihoods are rigs' `clamped` mode with a threshold of 0.3: at very low likelihoods the oracle's SVD and the
-kernel's eigen-solve legitimately disagree (header of test_tri_screen_gpu.py).
+its bars.  The likelihoods are rigs' `clamped` mode with a threshold of 0.3: at very low likelihoods the kernel's solve of the
+normal equations may leave the flat 1e-7 m bar (header of test_tri_screen_gpu.py); tests/test_tri_exact_gpu.py covers those.
 
 Thresholds follow the profile.  With undistortion the reference compares the UNDISTORTED observation with the reprojection
 through the ORIGINAL K and distortion (triangulation.py:473, quirk Q4), so a unit's error is about the mean displacement of

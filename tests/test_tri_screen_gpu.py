@@ -12,9 +12,11 @@ unguarded screen wrongly dropped about one winner per 13 k searching units there
 
 The `clamped` case of every rig family is also checked unit by unit against the C oracle with the bars of
 test_tri_gpu._compare.  The `low`, `zeros` and `heavy_light` cases are not: at a weight ratio of 1e-6 between the
-cameras of a unit (likelihood 1e-3 against 1) the system is one camera short of full rank to rounding, and the oracle's
-SVD and the kernel's eigen-solve legitimately disagree (tests/sweeps/fuzz_params.py raises such likelihoods for the same
-reason).  Screen on against screen off is the bar there.
+cameras of a unit (likelihood 1e-3 against 1) the oracle's SVD of A is still within 1e-9 m of the exact point
+(tests/test_tri_exact_host.py), but the kernel solves the normal equations A^T A, whose error there may pass the flat
+1e-7 m bar (tests/sweeps/fuzz_params.py raises such likelihoods for the same reason).  That error is bounded unit by unit
+by K e_cond in tests/test_tri_exact_gpu.py, against an exact multiprecision solve; here, screen on against screen off is
+the bar.
 """
 import os
 
