@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI in include/p2s.h and include/p2s_floor.h (csrc/libp2s_hip.so).
+"""ctypes binding of the C-ABI in include/p2s.h, include/p2s_floor.h and include/p2s_tri_frames.h (csrc/libp2s_hip.so).
 
 The library is the only compute path: there is no CPU fallback.  ``load()`` raises if the shared
 object is missing; ``Context()`` raises if no MI355X is visible.
@@ -208,6 +208,16 @@ FLOOR_SIGNATURES = {
     'p2s_floor_kernel_ms': (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
 }
 
+# and for include/p2s_tri_frames.h, triangulation with per-frame cameras
+TRI_FRAMES_SIGNATURES = {
+    'p2s_triangulate_frames_device': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                                C.c_void_p, C.c_void_p, C.POINTER(TriParams), C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
+    'p2s_triangulate_frames_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                              C.c_void_p, C.c_void_p, C.POINTER(TriParams), C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+}
+
 # entry points a library built before them lacks (P2S_LIB may name one): left unbound, and the feature is refused
 OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_host', 'p2s_json_gather_largest_person',
             'p2s_copy_files', 'p2s_reproject_host', 'p2s_reproject_kernel_ms', 'p2s_write_openpose_files',
@@ -220,7 +230,8 @@ OPTIONAL = {'p2s_gcv_spline_host', 'p2s_sync_speeds_host', 'p2s_lagged_pearson_h
             'p2s_track_persons_device', 'p2s_track_persons_kernel_ms', 'p2s_interpolate_gaps', 'p2s_fill_gaps', 'p2s_gap_runs',
             'p2s_gaps_kernel_ms', 'p2s_timeline_rows_host', 'p2s_timeline_kernel_ms', 'p2s_timeline_write_csv',
             'p2s_refine_extrinsics_host', 'p2s_refine_kernel_ms', 'p2s_refine_held_coord', 'p2s_relative_poses_host',
-            'p2s_relpose_kernel_ms', 'p2s_fit_planes_host', 'p2s_floor_kernel_ms'}
+            'p2s_relpose_kernel_ms', 'p2s_fit_planes_host', 'p2s_floor_kernel_ms', 'p2s_triangulate_frames_host',
+            'p2s_triangulate_frames_device'}
 
 _lib = None
 
@@ -238,7 +249,7 @@ def load():
         raise P2sError(f'{LIB_PATH} is missing: run `python -c "import __graft_entry__ as g; g.build()"` '
                        '(hipcc --offload-arch=gfx950). There is no CPU fallback.')
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **FLOOR_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **FLOOR_SIGNATURES, **TRI_FRAMES_SIGNATURES}.items():
         if name in OPTIONAL and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

@@ -115,6 +115,7 @@ int p2s_destroy(p2s_ctx *ctx) {
     for (Scratch &s : ctx->slot) s.release();
     ctx->wl_rec.release(); ctx->wl_count.release();
     ctx->deep_entries.release(); ctx->deep_ctl.release(); ctx->deep_sched.release(); ctx->deep_partials.release();
+    ctx->frames_sub.release(); ctx->frames_plan.release();
     if (ctx->d_cams) (void)hipFree(ctx->d_cams);
     if (ctx->d_binom) (void)hipFree(ctx->d_binom);
     if (ctx->d_stats) (void)hipFree(ctx->d_stats);
@@ -186,24 +187,8 @@ int p2s_set_calibration(p2s_ctx *ctx, int32_t n_cams, const double *P, const dou
     // (triangulation.py:411): what the fused kernel's lanes index by (level, rank); 2^C entries, C <= 16
     if (n_cams <= 16) {
         std::vector<uint16_t> tab;
-        std::vector<uint32_t> off(n_cams + 2, 0);
-        tab.reserve((size_t)1 << n_cams);
-        for (int k = 0; k <= n_cams; ++k) {
-            off[k] = (uint32_t)tab.size();
-            std::vector<int> idx(k);
-            for (int i = 0; i < k; ++i) idx[i] = i;
-            for (;;) {
-                uint32_t m = 0;
-                for (int i = 0; i < k; ++i) m |= 1u << idx[i];
-                tab.push_back((uint16_t)m);
-                int i = k - 1;
-                while (i >= 0 && idx[i] == n_cams - k + i) --i;
-                if (i < 0) break;
-                ++idx[i];
-                for (int j = i + 1; j < k; ++j) idx[j] = idx[j - 1] + 1;
-            }
-        }
-        off[n_cams + 1] = (uint32_t)tab.size();
+        std::vector<uint32_t> off;
+        p2s_subset_table(n_cams, tab, off);
         if (!ctx->d_sub_tab) HIP_TRY(hipMalloc((void **)&ctx->d_sub_tab, sizeof(uint16_t) << 16));
         if (!ctx->d_sub_off) HIP_TRY(hipMalloc((void **)&ctx->d_sub_off, sizeof(uint32_t) * 18));
         HIP_TRY(hipMemcpy(ctx->d_sub_tab, tab.data(), tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));

@@ -77,6 +77,10 @@ struct p2s_ctx {
     unsigned long long *d_assoc_stats = nullptr;     // 4 counters (p2s_get_assoc_stats)
     uint16_t *d_sub_tab = nullptr;                   // camera subsets by level (fused kernel), built with the calibration
     uint32_t *d_sub_off = nullptr;
+    // p2s_tri_frames.hip (per-frame cameras), independent of the static calibration above: the subset table of the last
+    // call's camera count (frames_sub_cams; the level offsets follow 2^16 table entries) and the wave plan of one call
+    Scratch frames_sub, frames_plan;
+    int frames_sub_cams = 0;
     // p2s_set_tuning: experiments and tests only, never read from the environment
     int tri_path = P2S_TRI_PATH_AUTO;
     int force_tiled = 0, no_overlap = 0, job = 0;
@@ -90,6 +94,31 @@ struct p2s_ctx {
     int pool_tiles = 5;                              // p2s_tri_pool.hip: tiles a wave streams before it searches their pooled failures (2..6)
     int poison = -1;                                 // 0..255: p2s_poison fills every context-owned buffer with this byte before a call uses it
 };
+
+// Every subset of n_cams <= 16 cameras as a bit mask, level by level in itertools.combinations order
+// (triangulation.py:411): what the lanes of the one-launch kernels index by (level, rank); 2^n_cams entries, level k
+// starts at off[k], off has n_cams + 2 entries.
+inline void p2s_subset_table(int n_cams, std::vector<uint16_t> &tab, std::vector<uint32_t> &off) {
+    tab.clear();
+    off.assign(n_cams + 2, 0);
+    tab.reserve((size_t)1 << n_cams);
+    for (int k = 0; k <= n_cams; ++k) {
+        off[k] = (uint32_t)tab.size();
+        std::vector<int> idx(k);
+        for (int i = 0; i < k; ++i) idx[i] = i;
+        for (;;) {
+            uint32_t m = 0;
+            for (int i = 0; i < k; ++i) m |= 1u << idx[i];
+            tab.push_back((uint16_t)m);
+            int i = k - 1;
+            while (i >= 0 && idx[i] == n_cams - k + i) --i;
+            if (i < 0) break;
+            ++idx[i];
+            for (int j = i + 1; j < k; ++j) idx[j] = idx[j - 1] + 1;
+        }
+    }
+    off[n_cams + 1] = (uint32_t)tab.size();
+}
 
 // P2S_TUNE_POISON_STAGING (tests only).  What an earlier call left in a staging slot or in one of the six role buffers of
 // the work-list triangulation (wl_rec, wl_count, deep_entries / ctl / sched / partials) is garbage by contract; with the

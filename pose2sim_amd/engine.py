@@ -550,6 +550,43 @@ class Engine:
                                                     _ptr(d_swap), C.byref(params), _ptr(d_Q), _ptr(d_err),
                                                     _ptr(d_nexcl), _ptr(d_mask)))
 
+    def triangulate_frames(self, xyl, P_frames, params, block_frame=None):
+        """Triangulation with per-frame cameras (a moving and / or zooming rig).  xyl: [F, C, K, 3] or [F, persons, C, K, 3]
+        float32/float64 host array; P_frames: [Fc, C, 3, 4].  Row f of the leading dimension uses calibration frame f, its
+        persons alike; block_frame ([blocks] int64, never decreasing) names the calibration frame of every block instead.
+        Needs no set_calibration and leaves it alone.  Returns what triangulate returns."""
+        xyl, dtype = as_packed(xyl)
+        P = np.ascontiguousarray(P_frames, dtype=np.float64)
+        if P.ndim != 4 or P.shape[2:] != (3, 4):
+            raise P2sError(f'P_frames has shape {P.shape}; expected [Fc, C, 3, 4]')
+        Fc, Cn = P.shape[:2]
+        if xyl.ndim not in (4, 5) or xyl.shape[-3] != Cn or xyl.shape[-1] != 3:
+            raise P2sError(f'xyl has shape {xyl.shape}; expected [F, {Cn}, K, 3] or [F, persons, {Cn}, K, 3]')
+        K = xyl.shape[-2]
+        lead = xyl.shape[:-3]
+        nb = int(np.prod(lead))
+        if block_frame is None:
+            block_frame = np.repeat(np.arange(lead[0], dtype=np.int64), nb // lead[0] if lead[0] else 0)
+        bf = np.ascontiguousarray(np.asarray(block_frame).reshape(-1), dtype=np.int64)
+        if bf.shape != (nb,):
+            raise P2sError(f'block_frame has {bf.size} entries; expected one per block, {nb}')
+        Q = np.empty((nb, K, 3), dtype=np.float64)
+        err = np.empty((nb, K), dtype=np.float32)
+        nex = np.empty((nb, K), dtype=np.uint8)
+        mask = np.empty((nb, K), dtype=np.uint32)
+        _lib.check(_entry(self._lib, 'p2s_triangulate_frames_host')(self._h, Fc, Cn, _ptr(P), nb, K, dtype, _ptr(xyl), _ptr(bf),
+                                                                    C.byref(params), _ptr(Q), _ptr(err), _ptr(nex), _ptr(mask)))
+        return (Q.reshape(lead + (K, 3)), err.reshape(lead + (K,)), nex.reshape(lead + (K,)), mask.reshape(lead + (K,)))
+
+    def triangulate_frames_device(self, n_cal_frames, n_cams, d_P, n_blocks, K, dtype, d_xyl, d_block_frame, params, d_Q, d_err,
+                                  d_nexcl, d_mask):
+        """Device-resident operands (tensors or raw pointers); enqueues on the engine's stream after reading
+        d_block_frame back once."""
+        _lib.check(_entry(self._lib, 'p2s_triangulate_frames_device')(self._h, int(n_cal_frames), int(n_cams), _ptr(d_P), int(n_blocks),
+                                                                      int(K), int(dtype), _ptr(d_xyl), _ptr(d_block_frame),
+                                                                      C.byref(params), _ptr(d_Q), _ptr(d_err), _ptr(d_nexcl),
+                                                                      _ptr(d_mask)))
+
     def timing_begin(self):
         _lib.check(self._lib.p2s_timing_begin(self._h))
 

@@ -74,35 +74,12 @@ def read_markers(trc_path):
 
 
 def read_cameras(calib_path):
-    """Every table but 'metadata' -> per camera: size, K ([3][3] or [Fp][3][3]), dist, rotation vector(s), translation(s)."""
-    tables = calib.load_toml(calib_path)
-    cams = []
-    for key in tables:
-        if key == 'metadata':
-            continue
-        t = tables[key]
-        cams.append({'S': np.array(t['size'], dtype=np.float64), 'K': np.array(t['matrix'], dtype=np.float64),
-                     'dist': np.array(t['distortions'], dtype=np.float64), 'R': np.array(t['rotation'], dtype=np.float64),
-                     'T': np.array(t['translation'], dtype=np.float64)})
-    return cams
+    """Every table but 'metadata' -> per camera: size, K ([3][3] or [Fp][3][3]), dist, rotation vector(s), translation(s)
+    (calib.read_cameras, the reader triangulation shares)."""
+    return calib.read_cameras(calib_path)
 
 
-def projection_matrices(cams):
-    """P [C][Fp][3][4] = [K | 0] [[R, T], [0, 1]]: Fp = 1 for static cameras, else one matrix per calibration frame of a
-    zooming (K per frame) and / or moving (rotation and translation per frame) camera."""
-    P = []
-    for cam in cams:
-        zooming, moving = cam['K'].ndim == 3, cam['R'].ndim == 2
-        n = len(cam['K']) if zooming else len(cam['R']) if moving else 1
-        per_frame = []
-        for f in range(n):
-            K = cam['K'][f] if zooming else cam['K']
-            rvec, T = (cam['R'][f], cam['T'][f]) if moving else (cam['R'], cam['T'])
-            H = np.block([[cvmath.rodrigues(rvec), T.reshape(3, 1)], [np.zeros(3), 1]])
-            per_frame.append(np.block([K, np.zeros((3, 1))]) @ H)
-        P.append(per_frame)
-    # cameras with different frame counts: NumPy refuses the ragged list here, as in the reference
-    return np.array(P).reshape(len(P), -1, 3, 4), any(c['K'].ndim == 3 or c['R'].ndim == 2 for c in cams)
+projection_matrices = calib.projection_matrices
 
 
 def labels_table(uv_cam, image_names, markers):
@@ -172,7 +149,7 @@ def reproj_from_trc_calib_func(engine=None, **args):
     cams = read_cameras(calib_path)
     P, per_frame = projection_matrices(cams)
     if undistort and per_frame:
-        raise NotImplementedError('undistort_points with moving or zooming cameras: the distorted projection takes static cameras only')
+        raise NotImplementedError(calib.UNDISTORT_PER_FRAME)
     sizes = np.array([cam['S'][:2] for cam in cams], dtype=np.float64).reshape(len(cams), 2)
 
     reproj_dir = os.path.realpath(out_root)

@@ -228,6 +228,32 @@ def summed_figures(person, sums, n):
             person.cam_fractions = {c: int(v) / total for c, v in enumerate(sums['cam_count'][n])}
 
 
+def load_frame_calibration(calib_file, undistort_points, handle_LR_swap):
+    """P [Fc][C][3][4] of a calibration with per-frame cameras (a moving and / or zooming rig), None for a static one.
+    What triangulation does not do with such a rig is refused here, on every rank, before any file is read."""
+    if not calib_mod.is_per_frame(calib_file):
+        return None
+    if undistort_points:
+        raise NotImplementedError(calib_mod.UNDISTORT_PER_FRAME)
+    if handle_LR_swap:
+        raise NotImplementedError('handle_LR_swap with moving or zooming cameras: the left / right swap search takes static cameras only')
+    if parallel.dist_info()[1] > 1:
+        raise NotImplementedError('moving or zooming cameras on more than one rank: triangulation with per-frame cameras runs on one GPU')
+    return calib_mod.frame_projections(calib_file)[0]
+
+
+def recap_px_to_m(first_cam, f_range):
+    """Pixels to metres for the report, through the first camera: |T| / fx; with per-frame
+    cameras the mean of |T(f)| / fx(f) over the frames of f_range."""
+    T = np.array(first_cam['translation'], dtype=np.float64)
+    K = np.array(first_cam['matrix'], dtype=np.float64)
+    if T.ndim == 1 and K.ndim == 2:
+        return float(np.sqrt(np.sum(T ** 2))) / first_cam['matrix'][0][0]
+    fr = np.arange(*f_range)
+    dist = np.sqrt(np.sum(T ** 2, axis=-1))
+    return float(np.mean((dist[fr] if T.ndim == 2 else dist) / (K[fr, 0, 0] if K.ndim == 3 else K[0, 0])))
+
+
 def triangulate_all(config_dict):
     """Same contract as the reference: reads <session>/calib*/*.toml and the pose JSON folders of
     config_dict['project']['project_dir'], writes <project>/pose-3d/<name>[_P<n>]_<f0>-<f1>.trc."""
@@ -253,8 +279,12 @@ def triangulate_all(config_dict):
     make_c3d = tcfg.get('make_c3d')
 
     calib_file = calib_mod.find_calibration_file(session_dir)
-    P = calib_mod.computeP(calib_file, undistort=undistort_points)
-    calib_params = calib_mod.retrieve_calib_params(calib_file)
+    P_frames = load_frame_calibration(calib_file, undistort_points, handle_LR_swap)    # None: static cameras
+    if P_frames is None:
+        P = calib_mod.computeP(calib_file, undistort=undistort_points)
+        calib_params = calib_mod.retrieve_calib_params(calib_file)
+    else:
+        P, calib_params = P_frames[0], None
 
     keypoints_ids, keypoints_names, keypoints_idx_swapped = skeletons.keypoints(pose_model, config_dict)
     keypoints_nb = len(keypoints_ids)
@@ -267,6 +297,9 @@ def triangulate_all(config_dict):
     f_range = [[0, min([len(j) for j in json_files_names])] if frame_range in ('all', 'auto', []) else frame_range][0]
     if n_cams != len(P):
         raise Exception(f'Error: The number of cameras is not consistent: Found {len(P)} cameras in the calibration file, and {n_cams} cameras based on the number of pose folders.')
+    if P_frames is not None and f_range[1] > len(P_frames):
+        raise ValueError(f'frame_range ends at frame {f_range[1]} but the calibration holds {len(P_frames)} frames: frame f is '
+                         'triangulated with calibration frame f')
 
     # ---- JSON -> packed tensor (native parser) -> HIP engine.  One process: every frame at once.  Several
     # ranks: each one reads, parses and triangulates only its contiguous block of frames (the ingest is the
@@ -290,10 +323,14 @@ def triangulate_all(config_dict):
         if not (multi_person and world == 1):
             xyl = poseio.load_observations(pose_dir, json_dirs_names, maps, my_range, keypoints_ids, nb_persons)
         engine = _make_engine()
-        engine.set_calibration(P, calib_params if undistort_points else None)
+        if P_frames is None:
+            engine.set_calibration(P, calib_params if undistort_points else None)
         prm = engine.tri_params(error_threshold, likelihood_threshold, min_cameras, undistort_points, handle_LR_swap)
         swap_arg = keypoints_idx_swapped if handle_LR_swap else None
-        if world > 1 and hasattr(engine, 'triangulate_packed') and parallel.collective_device().type == 'cuda':
+        if P_frames is not None:
+            # frame f of the .trc's Frame# column takes calibration frame f; the persons of a frame share its cameras
+            local = engine.triangulate_frames(xyl, P_frames, prm, block_frame=np.repeat(np.arange(*my_range), nb_persons))
+        elif world > 1 and hasattr(engine, 'triangulate_packed') and parallel.collective_device().type == 'cuda':
             # results stay on the GPU: the all-gather takes the packed device buffer as it is
             local = engine.triangulate_packed(xyl, prm, swap_arg, pad_blocks=parallel.largest_shard(n_frames, world) * nb_persons)
         else:
@@ -410,7 +447,7 @@ def recap_triangulate(config_dict, persons, keypoints_names, f_range, calib_file
     cal_keys = calib_mod.camera_keys(calib)
     cam_names = [calib[c].get('name') if calib[c].get('name') else c for c in cal_keys]
     first_cam = calib[cal_keys[0]]
-    px_to_m = float(np.sqrt(np.sum(np.array(first_cam['translation'], dtype=np.float64) ** 2))) / first_cam['matrix'][0][0]
+    px_to_m = recap_px_to_m(first_cam, f_range)
     kind = tcfg.get('interpolation')
     say = logging.info
 
